@@ -2,6 +2,14 @@
 
     python bench.py [--gpus N] [--steps K] [--warmup W]      (N > 1: starts N rank processes itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...   (one rank per GPU)
+    python bench.py --full ...                 (adds the per-kernel, roofline, synced and CPU legs below)
+    python bench.py --dump-outputs DIR ...     (what the last timed step computed, as DIR/<name>.npy)
+
+A plain run sets up, warms up, times the K steps and prints the line. `--full` adds everything else the
+line can carry: the per-launch breakdown of the last warm-up step (`kernels`), the dominant kernel's
+live average inside the timed region and its unshared step (`roofline`), the host-synced comparison
+steps (`synced_comparison`) and the CPU oracle (`cpu_baseline`); --kernel-events 0, --synced-steps 0
+and --cpu-baseline 0 switch single legs of it off. Those keys are null in a plain run's line.
 
 Workload (BASELINE.json configs[1]; per-GPU batch 24 = configs/train/vitl16/pretrain-256px-16f.yaml):
 ViT-L/16 RoPE encoder (24x1024, 16 heads), EMA target encoder, predictor 12x384 (12 heads), the two
@@ -9,9 +17,17 @@ reference mask configs (8 blocks @15 %, 2 blocks @70 %), masks from the referenc
 (torch seed 239 + rank), synthetic randn clips already resident in HBM. Weak scaling: every rank
 runs B=24 clips per step; RCCL all-reduce of the 326 M fp32 gradients per step for N > 1.
 
-Output: ONE JSON line (rank 0). `roofline` is the dominant kernel (largest total time) measured with
-HIP events around each of its launches inside the timed region; `cpu_baseline` times the CPU
-oracle (oracle/vjepa_oracle.py, fp32) on a bounded sample of the same workload.
+Output: ONE JSON line (rank 0). With --full, `roofline` is the dominant kernel (largest total time)
+measured with HIP events around each of its launches inside the timed region; `cpu_baseline` times the
+CPU oracle (oracle/vjepa_oracle.py, fp32) on a bounded sample of the same workload.
+
+--dump-outputs DIR (rank 0, after the timed steps and before any --full leg runs another step): the
+last timed step's loss (`loss.npy`) and what that step left in the trainer for its caller, the fp32
+master weights of the encoder, the predictor and the EMA target encoder, one file per flat arena
+(`encoder.npy`, `predictor.npy`, `encoder_nowd.npy`, `predictor_nowd.npy`, `target.npy`,
+`target_nowd.npy`), float32. An arena above DUMP_SAMPLE elements is written as a fixed seeded sample
+of that many elements (the same indices for the same arena size); the inputs depend only on the
+arguments, so two builds run with the same arguments can be compared file by file.
 """
 
 import argparse
@@ -109,7 +125,16 @@ def main():
     ap.add_argument("--rccl-proxy-cus", type=int, default=0,
                     help="with the reducer armed: a copy of 2x every bucket on N persistent workgroups beside its "
                          "all-reduce, pricing the CUs RCCL's channel kernels hold at world > 1 (diagnostic)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: per-kernel breakdown and roofline "
+                         "(--kernel-events), host-synced comparison steps (--synced-steps), CPU oracle (--cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (loss, updated fp32 weights) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not args.full:  # a plain run: set up, warm up, time the steps, print the line
+        args.cpu_baseline = args.kernel_events = args.synced_steps = 0
     if args.gpus > 1 and "RANK" not in os.environ:
         # no launcher: start one rank process per GPU from this GPU-free parent
         sys.exit(spawn_ranks(args.gpus))
@@ -227,6 +252,8 @@ def main():
     trainer.time_allreduce = False
     if prof:
         prof.stop()
+    if args.dump_outputs and rank == 0:  # before any --full leg below runs another step
+        dump_outputs(args.dump_outputs, loss, trainer)
     if world > 1:
         t = torch.tensor([elapsed], device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -347,6 +374,27 @@ def main():
         print(json.dumps(out), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 1 << 20  # elements written per arena (6 arenas: at most 24 MiB in all)
+
+
+def dump_outputs(path, loss, trainer):
+    """--dump-outputs: the last timed step's loss and the fp32 master weights it left behind (online
+    encoder, predictor, EMA target encoder), one float32 .npy per flat arena. Arenas above DUMP_SAMPLE
+    elements are sampled at fixed indices (CPU generator seeded by the arena's size, sorted)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(path, "loss.npy"), loss.detach().float().reshape(-1).cpu().numpy())
+    for a in trainer.opt.arenas + trainer.tgt_arenas:
+        flat = a.data.detach().reshape(-1)
+        if flat.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(flat.numel())
+            idx = torch.randint(flat.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+            flat = flat[idx.to(flat.device)]
+        np.save(os.path.join(path, a.name + ".npy"), flat.float().cpu().numpy())
 
 
 def _install_rccl_proxy(red, blocks, dev):

@@ -1,7 +1,7 @@
 """The ViT-L/16 pre-training config's training keys (configs/train/vitl16/pretrain-256px-16f.yaml,
-lines 1-98 of the reference), restated as a dict for the launcher tests: /root/reference does not
-exist on the GPU box. `micro()` shrinks batch / crop / frames / schedule so a test finishes in
-seconds; every other key keeps the config's value."""
+lines 1-98 of the reference), restated as a dict for the launcher tests; tests/test_launcher.py pins
+it against the file itself (tests/golden/pretrain-256px-16f.yaml). `micro()` shrinks batch / crop /
+frames / schedule so a test finishes in seconds; every other key keeps the config's value."""
 
 import copy
 

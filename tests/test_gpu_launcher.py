@@ -83,7 +83,7 @@ def test_rccl_with_too_few_devices_fails_loudly(tmp_path):
 
 
 def test_bench_gpus2_spawns_two_ranks():
-    r = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2",
+    r = _run([sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "2", "--full",
               "--crop", "64", "--frames", "8", "--model", "vit_small", "--cpu-baseline", "0", "--kernel-events", "0"],
              _env(VJ_DIST_BACKEND="gloo"), timeout=300)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

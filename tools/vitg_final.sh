@@ -12,7 +12,7 @@ out=gpurun_out/$tag; mkdir -p "$out"
 cp profiles/traffic.json "$out/traffic.json"
 run() {  # name workload bench-args...
   local name=$1 wl=$2; shift 2
-  timeout -k 10 400 python -u bench.py --steps 3 --warmup 2 --cpu-baseline 0 "$@" > "$out/$name.log" 2>&1 || { echo "$name failed"; tail -3 "$out/$name.log"; return 3; }
+  timeout -k 10 400 python -u bench.py --full --steps 3 --warmup 2 --cpu-baseline 0 "$@" > "$out/$name.log" 2>&1 || { echo "$name failed"; tail -3 "$out/$name.log"; return 3; }
   local dom
   dom=$(python3 -c "import json; print(json.loads([l for l in open('$out/$name.log') if l.startswith('{')][-1])['roofline']['kernel'])") || return 3
   echo "$name dominant: $dom"
@@ -23,7 +23,7 @@ run() {  # name workload bench-args...
   done
   python3 tools/traffic.py "$out/${name}_p1" "$out/${name}_p2" "$dom" "$out/traffic.json" "$wl" || return 5
   cp "$out/traffic.json" profiles/traffic.json  # the final line below reads it
-  timeout -k 10 400 python -u bench.py --steps 10 --warmup 3 --cpu-baseline 0 "$@" > "$out/${name}_final.log" 2>&1 || { echo "$name final failed"; return 3; }
+  timeout -k 10 400 python -u bench.py --full --steps 10 --warmup 3 --cpu-baseline 0 "$@" > "$out/${name}_final.log" 2>&1 || { echo "$name final failed"; return 3; }
   grep '^{' "$out/${name}_final.log" | tail -1 > "$out/${name}.json"
   cut -c1-600 "$out/${name}.json"
 }
