@@ -228,6 +228,13 @@ int vj_proxy_copy(void* dst, const void* src, long bytes, int blocks, int mode, 
  * it while its gradient all-reduce (app/vjepa/train.py:279-281, RCCL channel kernels) runs beside the
  * backward. Host state only (no device call). */
 int vj_set_reserved_cus(int n);
+/* Which 256-row GEMM kernel vj_gemm_bf16 (epi 0-4, 7) / vj_qkv_rope_gemm (epi 5) would run for a problem
+ * under the current VJ_GEMM_* environment knobs; host logic only (no device work; cus = CUs the choice is
+ * sized for, 0: the current device's). out6 = {tile rows 256 / 192, tile columns 256 / 128, waves 8 / 4,
+ * main loop 0 one-tile / 1 staggered 32-deep / 2 staggered 64-deep, workgroups per CU, tile rows per
+ * group of the tile order}. Returns VJ_ERR_UNSUPPORTED (3, out6 untouched) where that kernel declines the
+ * problem's epilogue or N; the size thresholds of the callers (M >= 1024, N >= 128) are theirs. */
+int vj_gemm256_plan(int M, int N, int K, int a_kmajor, int b_kmajor, int epi, int cus, int* out6);
 /* dst[c][r] = src[r][c] (bf16; rows, cols, strides multiples of 8): the K-major copy W^T that the
  * data-gradient GEMM dX = dY W (nn.Linear backward) reads as its B operand. */
 int vj_transpose_bf16(int rows, int cols, const void* src, long ld_src, void* dst, long ld_dst, void* stream);

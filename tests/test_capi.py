@@ -143,3 +143,81 @@ def test_hot_kernels_register_budgets():
     for k in hot:
         cap = max([b for pat, b in KNOWN_SCRATCH.items() if re.search(pat, k[".name"])], default=0)
         assert k[".private_segment_fixed_size"] <= cap, (k[".name"], k[".private_segment_fixed_size"], cap)
+
+
+KNOBS = ("VJ_GEMM_STG", "VJ_GEMM_STG64", "VJ_GEMM_BM192", "VJ_GEMM_2W", "VJ_GEMM_2W192", "VJ_GEMM_GROUP",
+         "VJ_GEMM_PXCD")
+BF16, F32_RESID, ROPE, PARTIAL = 0, 2, 5, 6  # ops.EPI_*
+
+
+def _plan(monkeypatch, M, N, K, epi, knobs=None, a_kmajor=1, b_kmajor=1, cus=256):
+    """vj_gemm256_plan under exactly `knobs`: None where the kernel declines, else a dict of its six outputs."""
+    import ctypes
+
+    from vjepa2_amd import _lib
+
+    for k in KNOBS:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in (knobs or {}).items():
+        monkeypatch.setenv(k, v)
+    out = (ctypes.c_int * 6)(*([-1] * 6))
+    rc = _lib.load().vj_gemm256_plan(M, N, K, a_kmajor, b_kmajor, epi, cus, out)
+    if rc == 3:  # VJ_ERR_UNSUPPORTED
+        assert list(out) == [-1] * 6
+        return None
+    assert rc == 0, _lib.last_error()
+    return dict(zip(("rows", "cols", "waves", "form", "per_cu", "group"), out))
+
+
+# (M, N, K, epilogue, knobs, expected subset of the plan); both operands K-major, 256 CUs
+PLAN_ROWS = [
+    (49152, 3072, 1024, ROPE, {}, dict(rows=256, cols=256, waves=8, form=2)),
+    (11712, 1024, 4096, F32_RESID, {}, dict(rows=256, cols=256, waves=8, form=2)),
+    # the cost model picks 192-row tiles, and form 1 does not apply with them
+    (2100, 512, 96, BF16, {}, dict(rows=192, cols=256, waves=8, form=0)),
+    (2100, 512, 96, BF16, {"VJ_GEMM_BM192": "0"}, dict(rows=256, cols=256, form=1)),
+    # an aux epilogue does not take form 1 unless forced
+    (2100, 512, 96, F32_RESID, {"VJ_GEMM_BM192": "0"}, dict(rows=256, cols=256, form=0)),
+    (2100, 512, 96, F32_RESID, {"VJ_GEMM_BM192": "0", "VJ_GEMM_STG": "1"}, dict(rows=256, cols=256, form=1)),
+    (71232, 384, 1024, F32_RESID, {}, dict(rows=192, cols=128, waves=4, per_cu=2)),
+    (71232, 384, 1024, ROPE, {}, dict(rows=256, cols=128, waves=4, per_cu=2)),
+    (71232, 384, 1024, F32_RESID, {"VJ_GEMM_2W": "0"}, dict(rows=256, cols=128, waves=8, form=0)),
+    # the 15 % rule makes 1152 and 1000 wide
+    (4096, 1152, 384, ROPE, {}, dict(rows=256, cols=256, form=2)),
+    (1333, 1000, 64, BF16, {"VJ_GEMM_BM192": "0"}, dict(rows=256, cols=256, form=2)),
+]
+
+
+def test_gemm256_plan_table(monkeypatch):
+    """The kernel choice of the 256-row GEMM as a host function: tile, waves and main-loop form per shape,
+    epilogue and knob setting."""
+    for M, N, K, epi, knobs, want in PLAN_ROWS:
+        got = _plan(monkeypatch, M, N, K, epi, knobs)
+        assert got is not None, (M, N, K, epi, knobs)
+        assert {k: got[k] for k in want} == want, (M, N, K, epi, knobs, got)
+        assert got["group"] == 4
+        if got["waves"] == 8:
+            assert got["per_cu"] == 1
+    # MN-major B: the one-tile kernel on 256 x 256 tiles
+    got = _plan(monkeypatch, 4096, 1024, 1024, BF16, b_kmajor=0)
+    assert got == dict(rows=256, cols=256, waves=8, form=0, per_cu=1, group=4), got
+    # split-K partial slabs are not a dispatch epilogue; N must be a multiple of 8
+    for M, N, K in ((4096, 1024, 1024), (2100, 384, 96), (256, 128, 64)):
+        for ak, bk in ((1, 1), (0, 0)):
+            assert _plan(monkeypatch, M, N, K, PARTIAL, a_kmajor=ak, b_kmajor=bk) is None
+    for N in (1020, 1028, 132, 4100):
+        for epi in (BF16, F32_RESID, ROPE):
+            assert _plan(monkeypatch, 4096, N, 1024, epi) is None
+    assert _plan(monkeypatch, 2100, 512, 96, BF16, {"VJ_GEMM_GROUP": "0"})["group"] == 0
+    assert _plan(monkeypatch, 2100, 512, 96, BF16, {"VJ_GEMM_GROUP": "8"})["group"] == 8
+
+
+def test_wgrad_splitk_column_rule_matches_plan(monkeypatch):
+    """ops.wgrad_splitk sizes its split for the column tiles the library picks (256 unless the last tile
+    would waste more than 15 %): its restatement of the rule agrees with the plan for every N."""
+    from vjepa2_amd import ops
+
+    for N in range(128, 8193, 8):
+        cols = _plan(monkeypatch, 4096, N, 1024, BF16, a_kmajor=0, b_kmajor=0)["cols"]
+        assert cols in (128, 256)
+        assert ops.wgrad_wide_tile(N) == (cols == 256), N

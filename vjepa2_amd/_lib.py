@@ -70,6 +70,7 @@ SIGNATURES = {
     "vj_cast_bf16": [_L, _P, _P, _P],
     "vj_proxy_copy": [_P, _P, _L, _I, _I, _P],
     "vj_set_reserved_cus": [_I],
+    "vj_gemm256_plan": [_I, _I, _I, _I, _I, _I, _I, ctypes.POINTER(_I)],
     "vj_transpose_bf16": [_I, _I, _P, _L, _P, _L, _P],
     "vj_transpose_bf16_batch": [_I, _P, _L, _P],
     "vj_swiglu_fwd": [_I, _I, _P, _L, _P, _L, _P],

@@ -60,7 +60,6 @@ def build(verbose=True, force=False, variant=None, defines=()):
     flags = CFLAGS + [f"-D{d}" for d in defines]
     flags.append(f"-DVJ_HEADER_CRC={header_crc()}u")
     if variant:
-        flags.append("-DVJ_VARIANT_BUILD=1")  # unlocks the timing-only VJ_DIAG_* macros (vj_common.h)
         # experiments: extra compiler flags for every source (e.g. VJ_EXTRA_FLAGS=-fno-slp-vectorize)
         flags += os.environ.get("VJ_EXTRA_FLAGS", "").split()
     os.makedirs(objdir, exist_ok=True)

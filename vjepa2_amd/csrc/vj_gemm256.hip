@@ -24,23 +24,6 @@
 #include <type_traits>
 #include "vj_gemm_tile.h"
 
-// Schedule choices fixed by round-3 measurements (the variants were removed from the source; the
-// numbers are in DESIGN.md and profiles/r03_gemm_*):
-//  * 8-wave main loop: only the A pieces of K-tile t + 2 go out after the barrier; the B pieces are
-//    issued after 3 of the last phase's 4 m-tiles (SPLIT_AT): -2..-7 % and a further 0..-5 % on the
-//    ViT-L shapes (r03_gemm_spread_kernels.txt,
-//    r03_gemm_split_kernels.txt). Also the A pieces after the first m-tile: slower.
-//  * on 256-wide bf16 tiles without a VALU-heavy epilogue only waves 0-3 issue the main-loop LDS-DMA
-//    (DMA_WAVES; their SIMD partners keep issuing MFMAs); the next tile's stage 1, issued around the
-//    epilogue, goes out from all 8 waves (r03_gemm_dmaw4_kernels.txt, r03_gemm_s1all_step_ab.txt).
-//    Slower and removed: the RoPE / GELU tiles on 4 DMA waves, A / B pieces split over waves 0-3 /
-//    4-7, the DMA from waves 4-7, s_setprio around the MFMA clusters or for waves 4-7.
-//  * one m-tile of residual / saved-derivative rows prefetched ahead in the direct epilogue (deeper:
-//    no faster, r03 stamps).
-constexpr int SPLIT_AT = 3;
-constexpr int DMA_WAVES = 4;
-constexpr int AUX_PF = 1;
-
 namespace {
 
 #if VJ_GEMM_STAMPS  // diagnostic build: s_memtime per tile (start, main loop done, epilogue done) of wave 0
@@ -62,108 +45,29 @@ __device__ __forceinline__ void vm_wait() {
   else asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
 }
 
-
-// NWV = 8: 8 waves (2 x 4), 64-deep K tiles, one workgroup per CU. NWV = 4 ("2W"): 4 waves (2 x 2),
-// TWO workgroups per CU, so one workgroup's epilogue (HBM / VALU) runs under the other's main loop
-// (MFMA); K-major operands only; 192 x 128 tiles 64 deep (80 KB, the default) or 256 x 128 tiles 32
-// deep (64 KB + the RoPE table area).
-// BMT = 192 (8-wave, K-major bf16, 256-wide direct-store tiles only): 96-row wave tiles (3 m-tiles
-// per M-half) for problems whose 256-row tile count leaves a round of CUs under-filled (context
-// GEMMs, M ~ 11.7k: 184 tiles of 256 x 256 on 256 CUs -> 244 tiles of 192 x 256).
-// VJ_STG_CPOL: cache-policy bits of the staggered loop's LDS-DMA pieces (0; sc1 = 16 measured within
-// noise, nt = 2 up to 2x slower). VJ_DIAG_NODMA / NOWAIT / SAMEADDR / FULL128: timing-only builds that
-// compute WRONG results (no DMA after the prologue; relaxed unit wait; every piece from one 1-KB block;
-// pieces of 8 whole 128-B rows) - profiles/r05_gemm_dma_diag.txt, never in the shipped library.
-#ifndef VJ_STG_CPOL
-#define VJ_STG_CPOL 0
-#endif
-#ifndef VJ_DIAG_NODMA
-#define VJ_DIAG_NODMA 0
-#endif
+// Geometry, schedule switches, LDS layout and the supported parameter combinations: Cfg256 (vj_gemm_tile.h)
 template <bool AK, bool BKM, int EPI, int BN, bool F8 = false, int NWV = 8, int BMT = 256, int STG = 0>
 __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
-  constexpr bool PART = EPI == EPI_PARTIAL || EPI == EPI_PARTIAL_RS;  // split-K partial slabs (RS: + row sums)
-  static_assert(!STG || (AK && BKM && !F8 && NWV == 8 && BMT == 256 && BN == 256 && !PART),
-                "staggered main loop: 8-wave K-major bf16 256 x 256 tiles");
-  static_assert(!F8 || (AK && BKM && !PART && EPI != EPI_GELU_BWD), "fp8: forward GEMMs only");
-  static_assert(NWV == 8 || (NWV == 4 && AK && BKM && !F8), "2-workgroup GEMM: K-major bf16 operands only");
-  constexpr int BM = BMT;
-  constexpr int MH = BM / 64;     // virtual 16-row m-tiles per half of the wave's rows (4 / 3)
-  // 2-workgroup kernels: 256 x 128 tiles 32 deep (64-B LDS rows), or 192 x 128 tiles 64 deep (128-B
-  // rows: whole cache lines per DMA piece, half the L1 -> L2 requests; 80 KB, no table: RoPE excluded)
-  constexpr int BK = (NWV == 8 || BMT == 192) ? 64 : 32;
-  constexpr int NT = NWV * 64;
-  constexpr int WNX = NWV / 2;  // waves across N (4 / 2)
-  constexpr int WMX = NWV / WNX;          // waves across M (2 / 4)
-  constexpr int WM = BM / WMX;            // wave tile rows (128 / 96)
-  constexpr int A_BYTES = BM * BK * 2;
-  constexpr int B_BYTES = BN * BK * 2;
-  constexpr int STAGE = A_BYTES + B_BYTES;
-  constexpr int WN = BN / WNX;    // wave tile columns (64 / 32)
-  constexpr int PB = 16;         // MFMA output block width
-  constexpr int NTN = WN / PB;    // n blocks per wave (4 / 2)
-  // LDS-DMA issuers: DMA_WAVES = 4 -> waves 0-3 only on 256-wide tiles (their SIMD partners 4-7 keep
-  // issuing MFMAs meanwhile), except the RoPE / GELU / GELU-backward tiles, whose next-tile stage 1
-  // goes out right before (or in) their VALU-heavy epilogue, where waves 0-3 would start it 16
-  // pieces late; 128-wide tiles (the predictor's N = 384) measured slower with it.
-  constexpr bool VALU_EPI = EPI == EPI_ROPE || EPI == EPI_GELU || EPI == EPI_GELU_BWD;
-  constexpr int DMAW = NWV != 8 ? NWV : (VALU_EPI || BN != 256 || F8) ? 8 : DMA_WAVES;
-  // K-major B with 4 n blocks per wave: permuted B staging + stores straight from registers (16-B
-  // f32 / 8-B bf16 per row); 128-wide tiles would store 4-8 B per lane, so they keep the LDS path
-  constexpr bool DIRECT = BKM && NTN == 4;
-  static_assert(BMT == 256 || (BMT == 192 && !F8 && AK && DIRECT && (NWV == 8 || EPI != EPI_ROPE)),
-                "192-row tiles: direct K-major bf16 (the 4-wave kernel without the RoPE table)");
-  constexpr bool AUX = EPI == EPI_F32_RESID || EPI == EPI_GELU_BWD || EPI == EPI_BF16_RESID;
-  constexpr bool F32OUT = EPI == EPI_F32 || EPI == EPI_F32_RESID || PART;
-
-  // The next tile's stage 0 is DMA'd during this tile's last K-tile. Its stage 1 goes out right
-  // after the last barrier, unless the epilogue still needs that LDS slot (staged epilogue: after
-  // it) or issues global loads that would queue behind the DMA in vmcnt order (AUX: once the last
-  // aux rows are fetched).
-  constexpr bool EARLY1 = DIRECT && !AUX;
-  // STG: ring of NSL 32-KB unit slots, DMA distance NSL - 2 units; 5 slots (all 160 KB of the CU's
-  // LDS, distance 3) unless the RoPE epilogue needs the table area (4 slots + table, distance 2)
-  // (GTAB: the GELU epilogue by table, 4 slots behind the 28.7-KB table at LDS offset 0, whose byte
-  // offsets then fit the 16-bit lanes the lookup computes them in)
-  constexpr bool GTAB = STG && EPI == EPI_GELU;
-#ifndef VJ_STG_NSL4
-#define VJ_STG_NSL4 0  // variant builds: every staggered kernel on 4 ring slots (distance 2)
-#endif
-  constexpr int NSL = STG ? ((EPI == EPI_ROPE || GTAB || VJ_STG_NSL4) ? 4 : 5) : 1;
-  constexpr int DIST = NSL - 2;
-  // S64 (STG == 2, round 6): the staggered loop on 64-deep K steps, so every 1-KB LDS-DMA piece is 8
-  // WHOLE 128-B rows (the 32-deep units above fetch 16 half lines: twice the L1 -> L2 requests, which
-  // bound that loop - profiles/r05_gemm_dma_diag.txt). The LDS budget is kept by splitting each K step
-  // of the tile into 16-KB granules of 128 rows x 64: A0 / A1 (tile rows 0-127 / 128-255) and Blo / Bhi
-  // (columns 0-127 / 128-255). Waves 0-3 stream the A granules, waves 4-7 the B granules, one granule
-  // per wave group and load interval (4 pieces per wave). A wave (wr, wc) owns rows {128 h + 64 wr +
-  // 0..63 : h = 0, 1} x columns 64 wc + 0..63; per K step it runs L0 (A0 and B fragments: 16
-  // ds_read_b128) | M0 (rows of A0: 32 MFMAs) | L1 (A1 fragments, B kept in registers: 8 reads) | M1,
-  // waves 4-7 one interval behind as before. Every output sums the same MFMAs in the same k order as
-  // the other forms: bitwise the same results. Rings: SA A slots, SB B slots (DMA distance SA - 1 /
-  // SB - 1 granules, 4 + 4 x 16 KB = the 4-slot ring's 128 KB, beside the GELU / RoPE tables).
-  constexpr bool S64 = STG == 2;
-  constexpr int GSZ = 16384;
-  // B ring depth (variant builds: VJ_S64_SB = 5 / 6 on the kernels without an LDS table). Deeper B
-  // rings removed the DMA stalls of a tile's first K steps (interval stamps) but slowed every later
-  // step: qkv tgt 260 -> 274 us, step -0.6 % (profiles/r06_gemm_s64.txt); 4 kept
-#ifndef VJ_S64_SB
-#define VJ_S64_SB 4
-#endif
-  constexpr int SA = 4, SB = (EPI == EPI_ROPE || GTAB) ? 4 : VJ_S64_SB;
-  constexpr int EA = SA - 1, EB = SB - 1;
+  using Cfg = Cfg256<AK, BKM, EPI, BN, F8, NWV, BMT, STG>;
+  static_assert(Cfg::supported, "k_gemm256: unsupported (layout, epilogue, tile) combination");
+  constexpr bool PART = Cfg::PART, RS = Cfg::RS, DIRECT = Cfg::DIRECT, AUX = Cfg::AUX, F32OUT = Cfg::F32OUT;
+  constexpr bool EARLY1 = Cfg::EARLY1, GTAB = Cfg::GTAB, S64 = Cfg::S64, ASYNC = Cfg::ASYNC;
+  constexpr int BM = Cfg::BM, MH = Cfg::MH, BK = Cfg::BK, NT = Cfg::NT, WNX = Cfg::WNX, WM = Cfg::WM, WN = Cfg::WN;
+  constexpr int PB = Cfg::PB, NTN = Cfg::NTN, A_BYTES = Cfg::A_BYTES, STAGE = Cfg::STAGE, DMAW = Cfg::DMAW;
+  constexpr int NSL = Cfg::NSL, DIST = Cfg::DIST, USZ = Cfg::USZ, GSZ = Cfg::GSZ, SA = Cfg::SA, SB = Cfg::SB;
+  constexpr int EA = Cfg::EA, EB = Cfg::EB, WRS = Cfg::WRS;
   static_assert(EA >= 2 && EB >= 3, "S64 waits assume at least one interval of DMA lead");
-  // first row of the wave's rows (S64: the wave's 64-row band in each 128-row half) and the first row
-  // of virtual m-tile i relative to it
-  constexpr int WRS = S64 ? 64 : WM;
+  static_assert(Cfg::SLOT_END <= Cfg::LDS_BYTES && Cfg::GTAB_END <= Cfg::LDS_BYTES && Cfg::RING_END <= Cfg::LDS_BYTES &&
+                    Cfg::S64_END <= Cfg::RING_END && Cfg::TAB_END <= Cfg::LDS_BYTES && Cfg::RTAB_END <= Cfg::LDS_BYTES &&
+                    Cfg::IMG_END <= Cfg::SLOT_END,
+                "an LDS region ends past the array");
+  static_assert(Cfg::lds_disjoint, "LDS regions overlap");
+  static_assert(Cfg::LDS_BYTES * Cfg::BLOCKS_PER_CU <= LDS_PER_CU, "the CU's workgroups exceed its LDS");
+  // first row of virtual m-tile i relative to the wave's first row (S64: two 64-row bands)
   auto rowoff = [](int i) { return S64 ? (i >> 2) * 128 + (i & 3) * 16 : i * 16; };
-  constexpr int RING0 = GTAB ? 32768 : 0;  // LDS offset of the STG ring
-  static_assert(!S64 || (SA + SB) * 16384 + RING0 + ((EPI == EPI_ROPE) ? TAB_BYTES : 0) <= 163840, "S64 rings exceed LDS");
-  constexpr int TABB = (NWV == 4 && BMT == 192) ? 0 : TAB_BYTES;  // 2 x 80 KB per CU leaves no table room
-  __shared__ __attribute__((aligned(16))) char smem_raw[GTAB ? RING0 + 4 * 32768 : STG && NSL == 5 ? 5 * 32768 : 2 * STAGE + TABB];
+  __shared__ __attribute__((aligned(16))) char smem_raw[Cfg::LDS_BYTES];
   LDS_AS char* smem = (LDS_AS char*)smem_raw;
-  LDS_AS char* tab = smem + 2 * STAGE;
-  [[maybe_unused]] LDS_AS char* ring = smem + RING0;
+  [[maybe_unused]] LDS_AS char* ring = smem + Cfg::RING0;
 
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -223,9 +127,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   auto load_k = [&](__amdgpu_buffer_rsrc_t ra, __amdgpu_buffer_rsrc_t rb, const Tile& T, int t, int slot,
                     int lane) {
     LDS_AS char* s = smem + slot * STAGE;
-#if VJ_DIAG_NODMA
-    if (t >= 2) return;
-#endif
     if (iss) {
       stage<AK, BM, false, DMAW, BK, WNX, PB>(ra, g.lda, g.M - T.m0, t * BK, T.Keff, s, wave, lane);
       stage<BKM, BN, DIRECT, DMAW, BK, WNX, PB>(rb, g.ldb, g.N - T.n0, t * BK, T.Keff, s + A_BYTES, wave, lane);
@@ -254,8 +155,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
     }
   }
   // tile-row positions (frame | row << 10 | col << 20) and the interleaved cos/sin table (RoPE)
-  [[maybe_unused]] LDS_AS int* rpos = (LDS_AS int*)tab;
-  [[maybe_unused]] LDS_AS f32x2* rtab = (LDS_AS f32x2*)(tab + BM * 4);
+  [[maybe_unused]] LDS_AS int* rpos = (LDS_AS int*)(smem + Cfg::RPOS_OFF);
+  [[maybe_unused]] LDS_AS f32x2* rtab = (LDS_AS f32x2*)(smem + Cfg::RTAB_OFF);
 
   int wg = run0 + jb;
   Tile cur = make_tile(wg);
@@ -268,7 +169,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   // of the 32 1-KB pieces of every unit (waves 0-3: A, 4-7: B; their lane offsets are fixed per
   // tile, the unit's K offset rides in soffset), 2 per load interval; past the stream end the pieces
   // zero-fill an unread slot, so the per-wave vmcnt count stays 4.
-  constexpr int USZ = 32768;
   [[maybe_unused]] const int nku = STG ? (g.K + 31) / 32 : 0;
   [[maybe_unused]] int dwg = wg, dku = 0, dpos = 0;
   [[maybe_unused]] __amdgpu_buffer_rsrc_t drs;
@@ -291,12 +191,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
           gr = (r - rl) + 4 * (rl & 15) + (rl >> 4);
         }
         dvo[j] = gr < left ? (uint32_t)(gr * ld * 2 + c * 16) : VJ_OOB;
-#if VJ_DIAG_FULL128
-        dvo[j] = (uint32_t)(((4 * (wave & 3) + j) * 8 + (lane >> 3)) * ld * 2 + (lane & 7) * 16);
-#endif
-#if VJ_DIAG_SAMEADDR
-        dvo[j] = (uint32_t)(lane * 16);
-#endif
       }
     } else {
 #pragma unroll
@@ -307,18 +201,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   auto dma_half = [&](auto h_c) {
     constexpr int h = decltype(h_c)::value;
     LDS_AS char* dst = ring + (dpos % NSL) * USZ + (isA ? 0 : 16384) + (4 * (wave & 3) + 2 * h) * 1024;
-#if VJ_DIAG_FULL128
-    const int soff = __builtin_amdgcn_readfirstlane((dku >> 1) * 128 + (dku & 1) * 128 * (int)(isA ? g.lda : g.ldb) * 2);
-#else
     const int soff = __builtin_amdgcn_readfirstlane(dku * 64);
-#endif
-#if VJ_DIAG_NODMA
-    if (dpos < DIST)
-#endif
-    {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst, 16, dvo[2 * h], soff, 0, VJ_STG_CPOL);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst + 1024, 16, dvo[2 * h + 1], soff, 0, VJ_STG_CPOL);
-    }
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst, 16, dvo[2 * h], soff, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst + 1024, 16, dvo[2 * h + 1], soff, 0, 0);
     if constexpr (h == 1) {
       ++dpos;
       if (++dku == nku) {
@@ -354,7 +239,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
     LDS_AS char* dst = ring + (isA ? dq % SA : SA + dq % SB) * GSZ + (wave & 3) * 4096;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + k * 1024, 16, dvo[k], soff, 0, VJ_STG_CPOL);
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + k * 1024, 16, dvo[k], soff, 0, 0);
     ++dq;
     if (++dk == 2 * nks) {
       dk = 0;
@@ -393,7 +278,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   }
   // GELU table: computed once per (persistent) workgroup under the first units' DMA; read only in the
   // epilogues, after the first tile's barriers
-  if constexpr (GTAB) gelu_tab_fill((LDS_AS f32x2*)smem, threadIdx.x, NT);
+  if constexpr (GTAB) gelu_tab_fill((LDS_AS f32x2*)(smem + Cfg::GTAB_OFF), threadIdx.x, NT);
 
   // Accumulators: acc[i][j] = m-tile i (16 rows), n block j; the epilogue walks the 2 * MH m-tiles,
   // 4 rows per lane (rows rowoff(i) + 4 (lane >> 4) + r of the wave tile).
@@ -452,7 +337,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   // band (so the 4 waves of a band cover its 8 m-tiles once), in M-half wc / 2, with v_dot2 against
   // bf16 ones: 4 VALU per m-tile and k-step beside 16 MFMAs, two f32 registers per lane (lane l:
   // row l & 15, k = 8 (l >> 4) .. + 7; the 4 lane groups are summed in the epilogue).
-  constexpr bool RS = EPI == EPI_PARTIAL_RS;
   [[maybe_unused]] float rsa = 0.f, rsb = 0.f;
   [[maybe_unused]] bool rs_on = false;
   auto rsum8 = [](const bf16x8& x, float s) {
@@ -496,7 +380,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   };
   // MN-major operands are read with asm transposed reads (ds_read_tr16_async): each phase first
   // waits for the fragments it consumes (read in the previous phase), then issues the next reads.
-  constexpr bool ASYNC = !AK || !BKM;
   auto release = [&](bf16x8 (&X)[MH], bf16x8 (&Y)[NTN]) {
     if constexpr (ASYNC) {
       lds_wait();
@@ -508,11 +391,19 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
 #if VJ_GEMM_STAMPS
   int stamp_it = 0;
 #endif
+  // One tile per iteration, in this order (the vmcnt counts of the main loops depend on it):
+  //  1. bookkeeping and prefetches (RoPE token ids, row-sum switch, fp8 scales, STG bias columns);
+  //  2. the main loop of the kernel's form (S64 | 32-deep staggered | one tile), whose tail DMAs the next
+  //     tile's stage 0, and its stage 1 where the epilogue neither needs the slot nor loads aux rows;
+  //  3. the epilogue (direct | staged), with the next tile's stage 1 behind its last aux fetch;
+  //  4. staged epilogue: the next tile's stage 1 into the image's slot;
+  //  5. barrier bookkeeping and the step to the next tile.
   for (;;) {
 #if VJ_GEMM_STAMPS
     const long st0 = __builtin_amdgcn_s_memtime();
     long st_k1 = 0;  // staggered loops: after the tile's first 64-deep K step
 #endif
+    // ---- 1. bookkeeping and prefetches
     const int wgn = wg + P;
     const bool has_next = wgn < runend;
     // the next tile's descriptors are rebuilt where they are used (SGPR pressure: 106 is the cap)
@@ -584,6 +475,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         }
       }
     };
+    // ---- 2. main loop
     if constexpr (S64) {
       // S64 main loop (above). Waits, with j = the group's load-interval index (A position j / B
       // position j are DMA'd EA / EB intervals ahead): waves 0-3 end every L with A position j + 1
@@ -717,12 +609,8 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
           if constexpr (DIST == 3) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
         } else {
-#if VJ_DIAG_NOWAIT
-          asm volatile("s_waitcnt vmcnt(24)" ::: "memory");
-#else
           if constexpr (DIST == 3) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
           else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-#endif
         }
         if (AUX && u == nku - 2) stg_aux();
         if (AUX && nku == 1) stg_aux();
@@ -812,7 +700,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (!TAIL) {
           if constexpr (SPREAD) {
-            if (iss && !VJ_DIAG_NODMA)
+            if (iss)
               stage<AK, BM, false, DMAW, BK, WNX, PB>(ra, g.lda, g.M - cur.m0, (t + 2) * BK, cur.Keff,
                                                        smem + sl * STAGE, wave, lane);
           } else {
@@ -832,7 +720,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
           }
         }
         auto b_pieces = [&] {
-          if (iss && !VJ_DIAG_NODMA)
+          if (iss)
             stage<BKM, BN, DIRECT, DMAW, BK, WNX, PB>(rb, g.ldb, g.N - cur.n0, (t + 2) * BK, cur.Keff,
                                                        smem + sl * STAGE + A_BYTES, wave, lane);
         };
@@ -877,7 +765,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       for (; t < nk; ++t) ktile(t, std::true_type{});
     }
 
-    // the epilogue's lane-derived addressing is recomputed per tile (an opaque copy of the lane id
+    // ---- 3. epilogue. Its lane-derived addressing is recomputed per tile (an opaque copy of the lane id
     // keeps the compiler from hoisting it out of the tile loop, where it would hold VGPRs across the
     // main loop)
 #if VJ_GEMM_STAMPS
@@ -946,15 +834,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
               dst[r][0] = x.x; dst[r][1] = x.y;
             }
           } else {
-            auto lo = [](uint32_t u) { return __builtin_bit_cast(float, u << 16); };  // bf16 -> f32, exact
-            auto hi = [](uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
             if constexpr (NTN == 4) {  // saved GELU derivative
               const uint2 x = *(const uint2*)((const bf16_t*)g.aux + off);
-              dst[r][0] = lo(x.x); dst[r][1] = hi(x.x);
-              dst[r][2] = lo(x.y); dst[r][3] = hi(x.y);
+              dst[r][0] = bf_lo(x.x); dst[r][1] = bf_hi(x.x);
+              dst[r][2] = bf_lo(x.y); dst[r][3] = bf_hi(x.y);
             } else {
               const uint32_t x = *(const uint32_t*)((const bf16_t*)g.aux + off);
-              dst[r][0] = lo(x); dst[r][1] = hi(x);
+              dst[r][0] = bf_lo(x); dst[r][1] = bf_hi(x);
             }
           }
         }
@@ -998,16 +884,14 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         for (int i = 0; i < AUX_PF; ++i) {
           if constexpr (STG) {  // m-tile 0, fetched under the last unit
             static_assert(AUX_PF == 1, "STG prefetches one m-tile of aux rows");
-            auto lo = [](float u) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, u) << 16); };
-            auto hi = [](float u) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, u) & 0xffff0000u); };
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               if constexpr (EPI == EPI_F32_RESID) {
 #pragma unroll
                 for (int j = 0; j < NTN; ++j) aux[0][r][j] = auxr[r][j];
               } else {
-                aux[0][r][0] = lo(auxr[r][0]); aux[0][r][1] = hi(auxr[r][0]);
-                aux[0][r][2] = lo(auxr[r][1]); aux[0][r][3] = hi(auxr[r][1]);
+                aux[0][r][0] = bf_lo(auxr[r][0]); aux[0][r][1] = bf_hi(auxr[r][0]);
+                aux[0][r][2] = bf_lo(auxr[r][1]); aux[0][r][3] = bf_hi(auxr[r][1]);
               }
             }
           } else {
@@ -1097,7 +981,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
               else
                 pk[r][q2] = pack_bf2(v[2 * q2], v[2 * q2 + 1]);
               if constexpr (EPI == EPI_GELU) {  // pk: the bf16 pre-activation -> GELU, derivative (if saved)
-                if constexpr (GTAB) ga[r][q2] = gelu_pair_tab<SAVE_D>(pk[r][q2], smem, &pk[r][q2]);
+                if constexpr (GTAB) ga[r][q2] = gelu_pair_tab<SAVE_D>(pk[r][q2], smem + Cfg::GTAB_OFF, &pk[r][q2]);
                 else ga[r][q2] = gelu_pair(pk[r][q2], SAVE_D ? &pk[r][q2] : nullptr);
               }
             }
@@ -1116,13 +1000,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       // ---- staged epilogue: passes of MTP m-tiles (16*MTP rows) per wave through a padded image in
       // the last K-tile's slot (free now; the next tile's stage 1 is DMA'd there afterwards): 2 m-tiles
       // per pass where the image fits the slot (BN = 128), else 1
-      constexpr int STR = WN + 4;    // floats per staged row (conflict-free ds_write_b32)
-      constexpr int LPR = WN / 4;    // lanes per staged row (16-B each)
-      constexpr int RPI = 64 / LPR;  // rows per wave-instruction
-      constexpr int MTP = (8 * 32 * STR * 4 <= STAGE) ? 2 : 1;
-      constexpr int PR = 16 * MTP;   // rows per pass
-      constexpr int IT = PR / RPI;   // row-instructions per pass
-      static_assert(8 * PR * STR * 4 <= STAGE, "staging image must fit one operand slot");
+      constexpr int STR = Cfg::STR, LPR = Cfg::LPR, RPI = Cfg::RPI, MTP = Cfg::MTP, PR = Cfg::PR, IT = Cfg::IT;
       LDS_AS float* wl = (LDS_AS float*)(smem + sle * STAGE + wave * PR * STR * 4);
       if constexpr (RS && MH == 4) {
         if (rs_on) {  // the row sums: lane groups (k sub-ranges) added, rows 32 wc + 16 (lane >> 4) + (lane & 15)
@@ -1218,20 +1096,17 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
             *(uint2*)((bf16_t*)g.C2 + (long)m * g.ldc2 + n) = make_uint2(a0, a1);
           } else if constexpr (EPI == EPI_BF16_RESID) {
             const uint2 pu = rpre[it];  // bf16 residual
-            auto lo = [](uint32_t u) { return __builtin_bit_cast(float, u << 16); };
-            auto hi = [](uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
             *(uint2*)((bf16_t*)g.C + (long)m * g.ldc + n) =
-                make_uint2(pack_bf2(lo(pu.x) + v[0], hi(pu.x) + v[1]), pack_bf2(lo(pu.y) + v[2], hi(pu.y) + v[3]));
+                make_uint2(pack_bf2(bf_lo(pu.x) + v[0], bf_hi(pu.x) + v[1]), pack_bf2(bf_lo(pu.y) + v[2], bf_hi(pu.y) + v[3]));
           } else {  // EPI_GELU_BWD
             const uint2 pu = rpre[it];  // saved GELU derivative (bf16)
-            auto lo = [](uint32_t u) { return __builtin_bit_cast(float, u << 16); };
-            auto hi = [](uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); };
             *(uint2*)((bf16_t*)g.C + (long)m * g.ldc + n) =
-                make_uint2(pack_bf2(v[0] * lo(pu.x), v[1] * hi(pu.x)), pack_bf2(v[2] * lo(pu.y), v[3] * hi(pu.y)));
+                make_uint2(pack_bf2(v[0] * bf_lo(pu.x), v[1] * bf_hi(pu.x)), pack_bf2(v[2] * bf_lo(pu.y), v[3] * bf_hi(pu.y)));
           }
         }
         __builtin_amdgcn_s_waitcnt(0xc07f);
       }
+      // ---- 4. the next tile's stage 1
       __syncthreads();  // every wave is done with its image before the slot is DMA'd
       if (has_next) {
         const Tile nxt = make_tile(wgn);
@@ -1250,6 +1125,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       ++stamp_it;
     }
 #endif
+    // ---- 5. barrier bookkeeping, next tile
     if constexpr (STG) {
       // waves 4-7: the barrier skipped after their last MFMAs (see the main loop); waves 0-3: the
       // matching one after the block's last tile, so both halves end with equal barrier counts
@@ -1274,6 +1150,25 @@ int num_cus() {
   return cus[dev];
 }
 
+// The environment knobs of the kernel choice, read per call (the tests change them between launches).
+// Switches: -1 = unset, else 0 / 1 (any other value counts as unset).
+struct Knobs {
+  int stg, stg64, bm192, w2, w2_192;
+  int group;  // VJ_GEMM_GROUP: -1 = unset, 0 = row-major, n = tile rows per group
+  int pxcd;   // VJ_GEMM_PXCD: blocks per XCD (0 = unset)
+};
+Knobs read_knobs() {
+  auto sw = [](const char* name) {
+    const char* e = getenv(name);
+    return e && (e[0] == '0' || e[0] == '1') ? e[0] - '0' : -1;
+  };
+  const char* grp = getenv("VJ_GEMM_GROUP");
+  const char* px = getenv("VJ_GEMM_PXCD");
+  return Knobs{sw("VJ_GEMM_STG"),   sw("VJ_GEMM_STG64"), sw("VJ_GEMM_BM192"),
+               sw("VJ_GEMM_2W"),    sw("VJ_GEMM_2W192"), grp ? (atoi(grp) > 0 ? atoi(grp) : 0) : -1,
+               px && atoi(px) > 0 ? atoi(px) : 0};
+}
+
 // Persistent grid: one block per CU (capped by the tile count), a multiple of 8 so every XCD gets
 // the same number of blocks. VJ_GEMM_PXCD caps the blocks per XCD (tests: many tiles per block).
 // (A phase offset between the blocks of an XCD, so odd blocks' epilogues fall under the even
@@ -1285,10 +1180,9 @@ int num_cus() {
 // profiles/r06_rccl_proxy_ab.txt). Set by distributed.GradReducer around its bucket window.
 std::atomic<int> g_reserved_cus{0};
 
-int grid256(long nb, int per_cu = 1) {
+int grid256(long nb, int per_cu, const Knobs& kn) {
   int per_xcd = per_cu * (num_cus() - g_reserved_cus.load(std::memory_order_relaxed)) / 8;
-  const char* e = getenv("VJ_GEMM_PXCD");
-  if (e && atoi(e) > 0) per_xcd = atoi(e);
+  if (kn.pxcd > 0) per_xcd = kn.pxcd;
   if (per_xcd < 1) per_xcd = 1;
   const long need = (nb + 7) / 8;
   return 8 * (int)(need < per_xcd ? need : per_xcd);
@@ -1302,208 +1196,129 @@ int grid256(long nb, int per_cu = 1) {
 // 8-or-row-major, +0.1 % over 8 on the tall ones with 4 on the rest (profiles/r04_gemm_group_ab.txt;
 // in isolation 8 is still ~1 % ahead on the target fc1 / QKV, 4 ahead on context QKV / dgrad).
 // VJ_GEMM_GROUP overrides (0 = row-major; tests: grouped order at small sizes).
-int tile_group(int tiles_m, int tiles_n) {
-  const char* e = getenv("VJ_GEMM_GROUP");
-  if (e) return atoi(e) > 0 ? atoi(e) : 0;
-  (void)tiles_m;
-  (void)tiles_n;
-  return 4;
-}
+int tile_group(const Knobs& kn) { return kn.group >= 0 ? kn.group : 4; }
 
-template <int BN>
-int launch256_f8(int epi, const G256& g, hipStream_t st) {
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n));
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((k_gemm256<true, true, EPI_BF16, BN, true>), grid, dim3(512), 0, st, g); break;
-    case EPI_F32: hipLaunchKernelGGL((k_gemm256<true, true, EPI_F32, BN, true>), grid, dim3(512), 0, st, g); break;
-    case EPI_F32_RESID:
-      hipLaunchKernelGGL((k_gemm256<true, true, EPI_F32_RESID, BN, true>), grid, dim3(512), 0, st, g);
-      break;
-    case EPI_GELU: hipLaunchKernelGGL((k_gemm256<true, true, EPI_GELU, BN, true>), grid, dim3(512), 0, st, g); break;
-    case EPI_ROPE: hipLaunchKernelGGL((k_gemm256<true, true, EPI_ROPE, BN, true>), grid, dim3(512), 0, st, g); break;
-    default: vj_set_error("vj_gemm_fp8: unsupported epilogue %d", epi); return VJ_ERR_ARG;
+// 256-wide column tiles unless the last one would waste more than 15 % of the work (measured,
+// tools/bench_kernels.py: predictor QKV N = 1152 -17 % with 256-wide tiles; N = 384 +14 %; 256-wide
+// tiles for every N > 256: DESIGN.md). The split-K weight gradients take the same rule: ViT-g's
+// N = 1408 runs 6 tiles of 256 instead of 11 of 128 (twice the work per operand byte).
+bool wide_tile_ok(int N) { return N % 256 == 0 || (N > 256 && vj_cdiv(N, 256) * 256L * 100 <= 115L * N); }
+
+// Which kernel a GEMM gets: tile rows (256 / 192) x columns (256 / 128), waves (8 / 4), main loop
+// (stg: 0 = one tile, 1 = staggered 32-deep units, 2 = S64), workgroups per CU and the tile group.
+struct Plan256 {
+  bool ok;  // false: the 256-row kernel declines the problem
+  int bm, bn, waves, stg, per_cu, group;
+};
+
+// The choice, a pure function of the problem, the CU count and the knobs.
+//  * 4 waves, two workgroups per CU (NWV = 4), for K-major GEMMs whose N needs 128-wide tiles: the
+//    direct-store epilogue overlaps the other workgroup's MFMAs. Measured (tools/bench_kernels.py):
+//    predictor fc2 N = 384 (f32 residual epilogue) -14 %, N = 384 bf16 even; on 256-wide shapes the
+//    32-deep main loop loses 10-20 %, so they stay on the 8-wave kernel. VJ_GEMM_2W: 0 = never, 1 = every
+//    K-major GEMM, unset = the 128-wide shapes. Its tiles are 192 x 128, 64 deep: each 1-KB DMA piece is
+//    8 whole 128-B rows, where 256 x 128 tiles' 32-deep pieces fetch 16 half lines (twice the L1 -> L2
+//    requests, which bound that kernel: profiles/r05_gemm_dma_diag.txt). Bitwise the same outputs;
+//    predictor fc2 132 -> 115 us, QKV / proj data gradients -8..-11 %, step +0.4 %
+//    (profiles/r05_gemm_2w192_ab.txt). VJ_GEMM_2W192=0 restores the 256 x 128 form; RoPE keeps it (no
+//    room for its table at 2 x 80 KB).
+//  * staggered main loops for the K-major 256 x 256-tile GEMMs: form 1 = 32-deep units (K % 32 == 0),
+//    form 2 = S64, 64-deep whole-line granules (K % 64 == 0). Measured, round 4
+//    (profiles/r04_gemm_staggered_step.txt): form 1 pays on the GELU / RoPE / bf16 / f32 epilogues
+//    (-1.6..-1.8 % in the step) and not on the residual / saved-derivative ones. Round 6
+//    (profiles/r06_gemm_s64.txt): isolated, S64 runs a K step 3-4 % faster where the operand panels
+//    stream from beyond L2 (K = 4096: target fc2 -2.4..-4 %) and takes the residual epilogues below the
+//    one-tile kernel (target proj / fc2, bf16 or f32 residual, -1..-4 %), but is 4-12 % slower per K step
+//    on the L2-resident K = 1024 panels of the QKV / GELU / RoPE / data-gradient GEMMs; in the train step,
+//    where the side streams' GEMMs share the chip (and its L2), S64 on every shape beats both the round-5
+//    choice (+0.8 %) and S64 only on K >= 2048 and the residual epilogues (+0.55 %), two interleaved runs
+//    each in one call. Default: S64 wherever K % 64 == 0, else form 1 on the epilogues without aux rows.
+//    VJ_GEMM_STG: 0 = never, 1 = every epilogue (form 1 where S64 cannot run); VJ_GEMM_STG64: 0 / 1
+//    forces form 1 / 2 wherever a staggered loop runs.
+//  * 192-row tiles (one-tile main loop) for a K-major 256-wide GEMM whose rounds of tiles over the CUs
+//    cost clearly less than with 256 rows: rounds x rows, 192-row tiles charged 8 % for their lower
+//    MFMA : fragment-read ratio (measured 6-9 % on full-round shapes), and at least 15 % predicted gain
+//    (a predictor step whose M made the 8 % rule pick 192 ran its fc1 / dgrad slower). Where S64 can run
+//    instead, the 256-row S64 tiles measured +0.2 % per step over the cost model's 192-row picks (the
+//    context GEMMs, M ~ 11.7k; VJ_GEMM_BM192=0 vs default, two same-call runs each,
+//    profiles/r06_gemm_s64.txt). VJ_GEMM_BM192: 0 = never, 1 = always, unset = the cost model.
+Plan256 plan256(int M, int N, int K, bool a_kmajor, bool b_kmajor, int epi, int cus, const Knobs& kn) {
+  if (epi < EPI_BF16 || (epi > EPI_ROPE && epi != EPI_BF16_RESID) || N % 8) return Plan256{false};
+  Plan256 p{true, 256, wide_tile_ok(N) ? 256 : 128, 8, 0, 1, tile_group(kn)};
+  if (!a_kmajor || !b_kmajor) return p;
+  if (kn.w2 >= 0 ? kn.w2 : p.bn == 128) {
+    p.bn = 128;
+    p.waves = 4;
+    p.per_cu = 2;
+    if (kn.w2_192 != 0 && epi != EPI_ROPE) p.bm = 192;
+    return p;
   }
-  VJ_LAUNCH_CHECK("vj_gemm_fp8");
-  return VJ_OK;
-}
-
-// Two-workgroups-per-CU kernel (NWV = 4, 256 x 128 tiles, 32-deep K) for K-major GEMMs whose N
-// needs 128-wide tiles: its direct-store epilogue overlaps the other workgroup's MFMAs. Measured
-// (tools/bench_kernels.py): predictor fc2 N = 384 (f32 residual epilogue) -14 %, N = 384 bf16 even;
-// on 256-wide shapes its 32-deep main loop loses 10-20 %, so they stay on the 8-wave kernel.
-// VJ_GEMM_2W: 0 = never, 1 = every K-major GEMM, unset = the 128-wide shapes.
-int use_2w(bool narrow) {
-  const char* e = getenv("VJ_GEMM_2W");
-  if (e && e[0] == '0') return 0;
-  if (e && e[0] == '1') return 1;
-  return narrow ? 1 : 0;
-}
-
-int launch2w(int epi, G256 g, hipStream_t st) {
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n, 2));
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((k_gemm256<true, true, EPI_BF16, 128, false, 4>), grid, dim3(256), 0, st, g); break;
-    case EPI_F32: hipLaunchKernelGGL((k_gemm256<true, true, EPI_F32, 128, false, 4>), grid, dim3(256), 0, st, g); break;
-    case EPI_F32_RESID:
-      hipLaunchKernelGGL((k_gemm256<true, true, EPI_F32_RESID, 128, false, 4>), grid, dim3(256), 0, st, g);
-      break;
-    case EPI_GELU: hipLaunchKernelGGL((k_gemm256<true, true, EPI_GELU, 128, false, 4>), grid, dim3(256), 0, st, g); break;
-    case EPI_GELU_BWD:
-      hipLaunchKernelGGL((k_gemm256<true, true, EPI_GELU_BWD, 128, false, 4>), grid, dim3(256), 0, st, g);
-      break;
-    case EPI_ROPE: hipLaunchKernelGGL((k_gemm256<true, true, EPI_ROPE, 128, false, 4>), grid, dim3(256), 0, st, g); break;
-    case EPI_BF16_RESID:
-      hipLaunchKernelGGL((k_gemm256<true, true, EPI_BF16_RESID, 128, false, 4>), grid, dim3(256), 0, st, g);
-      break;
-    default: vj_set_error("gemm2w: bad epilogue %d", epi); return VJ_ERR_ARG;
+  if (p.bn == 128) return p;
+  if (K % 32 == 0 && kn.stg != 0) {
+    const bool aux = epi == EPI_F32_RESID || epi == EPI_BF16_RESID || epi == EPI_GELU_BWD;
+    p.stg = (kn.stg64 == 0 || K % 64) ? 1 : 2;
+    if (aux && p.stg == 1 && kn.stg != 1) p.stg = 0;
   }
-  VJ_LAUNCH_CHECK("vj_gemm256(2w)");
-  return VJ_OK;
-}
-
-// The 4-wave two-workgroup kernel on 192 x 128 tiles, 64 deep: each 1-KB DMA piece is 8 whole 128-B
-// rows, where the 256 x 128 tiles' 32-deep pieces fetch 16 half lines (twice the L1 -> L2 requests,
-// which bound that kernel: profiles/r05_gemm_dma_diag.txt). Bitwise the same outputs; predictor fc2
-// 132 -> 115 us, QKV / proj data gradients -8..-11 %, step +0.4 % (profiles/r05_gemm_2w192_ab.txt).
-// VJ_GEMM_2W192=0 restores the 256 x 128 form; RoPE keeps it (no room for its table at 2 x 80 KB).
-int launch2w192(int epi, G256 g, hipStream_t st) {
-  g.tiles_m = vj_cdiv(g.M, 192);
-  g.group = tile_group(g.tiles_m, g.tiles_n);
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n, 2));
-#define L2W(E) hipLaunchKernelGGL((k_gemm256<true, true, E, 128, false, 4, 192>), grid, dim3(256), 0, st, g); break
-  switch (epi) {
-    case EPI_BF16: L2W(EPI_BF16);
-    case EPI_F32: L2W(EPI_F32);
-    case EPI_F32_RESID: L2W(EPI_F32_RESID);
-    case EPI_GELU: L2W(EPI_GELU);
-    case EPI_GELU_BWD: L2W(EPI_GELU_BWD);
-    case EPI_BF16_RESID: L2W(EPI_BF16_RESID);
-    default: vj_set_error("gemm2w192: bad epilogue %d", epi); return VJ_ERR_ARG;
+  if (p.stg == 2 && kn.bm192 != 1) return p;
+  const long tn = vj_cdiv(N, 256);
+  const long r256 = (vj_cdiv(M, 256) * tn + cus - 1) / cus, r192 = (vj_cdiv(M, 192) * tn + cus - 1) / cus;
+  if (kn.bm192 >= 0 ? kn.bm192 : r192 * 192 * 108 < r256 * 256 * 85) {
+    p.bm = 192;
+    p.stg = 0;
   }
-#undef L2W
-  VJ_LAUNCH_CHECK("vj_gemm256(2w192)");
-  return VJ_OK;
-}
-bool use_2w192(int epi) {
-  const char* e = getenv("VJ_GEMM_2W192");
-  return !(e && e[0] == '0') && epi != EPI_ROPE;
+  return p;
 }
 
-// one-tile launch; 192-row tiles (BMT = 192) for the K-major 256-wide shapes use_bm192() picks
-int launch192(int epi, const G256& g, hipStream_t st) {
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n));
-#define L192(E) hipLaunchKernelGGL((k_gemm256<true, true, E, 256, false, 8, 192>), grid, dim3(512), 0, st, g); break
-  switch (epi) {
-    case EPI_BF16: L192(EPI_BF16);
-    case EPI_F32: L192(EPI_F32);
-    case EPI_F32_RESID: L192(EPI_F32_RESID);
-    case EPI_GELU: L192(EPI_GELU);
-    case EPI_GELU_BWD: L192(EPI_GELU_BWD);
-    case EPI_ROPE: L192(EPI_ROPE);
-    case EPI_BF16_RESID: L192(EPI_BF16_RESID);
-    default: vj_set_error("gemm192: bad epilogue %d", epi); return VJ_ERR_ARG;
+// The runtime epilogue -> kernel instantiation, for one set of the other template parameters: the one
+// list of epilogues, instantiated where Cfg256 supports the combination.
+template <int... E>
+struct EpiList {};
+using Epilogues = EpiList<EPI_BF16, EPI_F32, EPI_F32_RESID, EPI_GELU, EPI_GELU_BWD, EPI_ROPE, EPI_PARTIAL, EPI_BF16_RESID,
+                          EPI_PARTIAL_RS>;
+
+template <bool AK, bool BKM, int EPI, int BN, bool F8, int NWV, int BMT, int STG>
+int launch_epi256(const G256& g, hipStream_t st, const Knobs& kn) {
+  using Cfg = Cfg256<AK, BKM, EPI, BN, F8, NWV, BMT, STG>;
+  if constexpr (Cfg::supported) {
+    const dim3 grid(grid256((long)g.tiles_m * g.tiles_n * g.nsplit, Cfg::BLOCKS_PER_CU, kn));
+    hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI, BN, F8, NWV, BMT, STG>), grid, dim3(Cfg::THREADS), 0, st, g);
+    VJ_LAUNCH_CHECK("vj_gemm256");
+    return VJ_OK;
+  } else {
+    return VJ_ERR_UNSUPPORTED;
   }
-#undef L192
-  VJ_LAUNCH_CHECK("vj_gemm256(192)");
-  return VJ_OK;
 }
 
-// Tile rows for a K-major 256-wide GEMM: 192 when its rounds of tiles over the CUs cost clearly less
-// than with 256 rows: rounds x rows, 192-row tiles charged 8 % for their lower MFMA : fragment-read
-// ratio (measured 6-9 % on full-round shapes), and at least 15 % predicted gain (a predictor step
-// whose M made the 8 % rule pick 192 ran its fc1 / dgrad slower). Context GEMMs (M ~ 11.7k,
-// N = 1024 / 3072) take 192; the target / predictor shapes keep 256. VJ_GEMM_BM192: 0 = never,
-// 1 = always, unset = the cost model.
-bool use_bm192(int M, int tn) {
-  const char* e = getenv("VJ_GEMM_BM192");
-  if (e && e[0] == '0') return false;
-  if (e && e[0] == '1') return true;
-  const long cus = num_cus();
-  const long r256 = ((long)vj_cdiv(M, 256) * tn + cus - 1) / cus;
-  const long r192 = ((long)vj_cdiv(M, 192) * tn + cus - 1) / cus;
-  return r192 * 192 * 108 < r256 * 256 * 85;
+template <bool AK, bool BKM, int BN, bool F8, int NWV, int BMT, int STG, int... E>
+int launch_list256(int epi, const G256& g, hipStream_t st, const Knobs& kn, EpiList<E...>) {
+  int rc = -1;
+  (void)((epi == E && ((rc = launch_epi256<AK, BKM, E, BN, F8, NWV, BMT, STG>(g, st, kn)), true)) || ...);
+  if (rc >= 0) return rc;
+  vj_set_error("vj_gemm256: bad epilogue %d", epi);
+  return VJ_ERR_ARG;
+}
+template <bool AK, bool BKM, int BN, bool F8 = false, int NWV = 8, int BMT = 256, int STG = 0>
+int launch256(int epi, const G256& g, hipStream_t st, const Knobs& kn) {
+  return launch_list256<AK, BKM, BN, F8, NWV, BMT, STG>(epi, g, st, kn, Epilogues{});
 }
 
-// Staggered main loop (STG) for the K-major 256 x 256-tile GEMMs: form 1 = 32-deep units (K % 32 == 0),
-// form 2 = S64, 64-deep whole-line granules (K % 64 == 0); 0 = the one-tile kernel. Measured, round 4
-// (profiles/r04_gemm_staggered_step.txt): form 1 pays on the GELU / RoPE / bf16 / f32 epilogues (-1.6..-1.8 %
-// in the step) and not on the residual / saved-derivative ones. Round 6 (profiles/r06_gemm_s64.txt):
-// isolated, S64 runs a K step 3-4 % faster where the operand panels stream from beyond L2 (K = 4096:
-// target fc2 -2.4..-4 %) and takes the residual epilogues below the one-tile kernel (target proj / fc2,
-// bf16 or f32 residual, -1..-4 %), but is 4-12 % slower per K step on the L2-resident K = 1024 panels of
-// the QKV / GELU / RoPE / data-gradient GEMMs; in the train step, where the side streams' GEMMs share the
-// chip (and its L2), S64 on every shape beats both the round-5 choice (+0.8 %) and S64 only on K >= 2048
-// and the residual epilogues (+0.55 %), two interleaved runs each in one call. Default: S64 wherever
-// K % 64 == 0, else form 1 on the epilogues without aux rows. VJ_GEMM_STG: 0 = never, 1 = every epilogue
-// (form 1 where S64 cannot run); VJ_GEMM_STG64: 0 / 1 forces form 1 / 2 wherever a staggered loop runs.
-int use_stg(int K, int epi) {
-  if (K % 32) return 0;
-  const char* e = getenv("VJ_GEMM_STG");
-  if (e && e[0] == '0') return 0;
-  const bool aux = epi == EPI_F32_RESID || epi == EPI_BF16_RESID || epi == EPI_GELU_BWD;
-  int form = 2;
-  const char* f = getenv("VJ_GEMM_STG64");
-  if (f && f[0] == '0') form = 1;
-  if (f && f[0] == '1') form = 2;
-  if (form == 2 && K % 64) form = 1;
-  if (aux && form == 1 && !(e && e[0] == '1')) return 0;
-  return form;
-}
-
-template <int FORM>
-int launch_stg(int epi, const G256& g, hipStream_t st) {
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n));
-#define LSTG(E) hipLaunchKernelGGL((k_gemm256<true, true, E, 256, false, 8, 256, FORM>), grid, dim3(512), 0, st, g); break
-  switch (epi) {
-    case EPI_BF16: LSTG(EPI_BF16);
-    case EPI_F32: LSTG(EPI_F32);
-    case EPI_F32_RESID: LSTG(EPI_F32_RESID);
-    case EPI_GELU: LSTG(EPI_GELU);
-    case EPI_GELU_BWD: LSTG(EPI_GELU_BWD);
-    case EPI_ROPE: LSTG(EPI_ROPE);
-    case EPI_BF16_RESID: LSTG(EPI_BF16_RESID);
-    default: vj_set_error("gemm256(stg): bad epilogue %d", epi); return VJ_ERR_ARG;
+// the planned kernel on g (tiles_m, tiles_n and group are set from the plan)
+int launch_plan(const Plan256& p, bool ak, bool bkm, int epi, G256& g, hipStream_t st, const Knobs& kn) {
+  g.tiles_m = vj_cdiv(g.M, p.bm);
+  g.tiles_n = vj_cdiv(g.N, p.bn);
+  g.group = p.group;
+  if (p.waves == 4)
+    return p.bm == 192 ? launch256<true, true, 128, false, 4, 192>(epi, g, st, kn)
+                       : launch256<true, true, 128, false, 4, 256>(epi, g, st, kn);
+  if (p.bm == 192) return launch256<true, true, 256, false, 8, 192>(epi, g, st, kn);
+  if (p.stg == 2) return launch256<true, true, 256, false, 8, 256, 2>(epi, g, st, kn);
+  if (p.stg == 1) return launch256<true, true, 256, false, 8, 256, 1>(epi, g, st, kn);
+  if (p.bn == 256) {
+    if (ak) return bkm ? launch256<true, true, 256>(epi, g, st, kn) : launch256<true, false, 256>(epi, g, st, kn);
+    return bkm ? launch256<false, true, 256>(epi, g, st, kn) : launch256<false, false, 256>(epi, g, st, kn);
   }
-#undef LSTG
-  VJ_LAUNCH_CHECK("vj_gemm256(stg)");
-  return VJ_OK;
-}
-
-template <bool AK, bool BKM, int BN>
-int launch256(int epi, const G256& g, hipStream_t st) {
-  const dim3 grid(grid256((long)g.tiles_m * g.tiles_n * g.nsplit));
-  switch (epi) {
-    case EPI_BF16: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_BF16, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_F32: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_F32, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_F32_RESID: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_F32_RESID, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_GELU: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_GELU, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_GELU_BWD: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_GELU_BWD, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_ROPE: hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_ROPE, BN>), grid, dim3(512), 0, st, g); break;
-    case EPI_BF16_RESID:  // forward GEMMs only (A and B K-major); other layouts take the generic kernel
-      if constexpr (AK && BKM) {
-        hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_BF16_RESID, BN>), grid, dim3(512), 0, st, g);
-        break;
-      } else {
-        return VJ_ERR_UNSUPPORTED;
-      }
-    case EPI_PARTIAL:  // split-K weight gradients only: dY^T X, both operands MN-major
-      if constexpr (!AK && !BKM) {
-        hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_PARTIAL, BN>), grid, dim3(512), 0, st, g);
-        break;
-      } else {
-        return VJ_ERR_UNSUPPORTED;
-      }
-    case EPI_PARTIAL_RS:  // the same with the fused bias gradient (g.rsum)
-      if constexpr (!AK && !BKM) {
-        hipLaunchKernelGGL((k_gemm256<AK, BKM, EPI_PARTIAL_RS, BN>), grid, dim3(512), 0, st, g);
-        break;
-      } else {
-        return VJ_ERR_UNSUPPORTED;
-      }
-    default: vj_set_error("gemm256: bad epilogue %d", epi); return VJ_ERR_ARG;
-  }
-  VJ_LAUNCH_CHECK("vj_gemm256");
-  return VJ_OK;
+  if (ak) return bkm ? launch256<true, true, 128>(epi, g, st, kn) : launch256<true, false, 128>(epi, g, st, kn);
+  return bkm ? launch256<false, true, 128>(epi, g, st, kn) : launch256<false, false, 128>(epi, g, st, kn);
 }
 
 }  // namespace
@@ -1514,13 +1329,17 @@ extern "C" int vj_set_reserved_cus(int n) {
   return VJ_OK;
 }
 
-// 256-wide column tiles unless the last one would waste more than 15 % of the work (measured,
-// tools/bench_kernels.py: predictor QKV N = 1152 -17 % with 256-wide tiles; N = 384 +14 %)
-#ifndef VJ_WIDE_ALL
-#define VJ_WIDE_ALL 0  // variant builds: 256-wide column tiles for every N > 256
-#endif
-bool wide_tile_ok(int N) {
-  return N % 256 == 0 || (N > 256 && (VJ_WIDE_ALL || vj_cdiv(N, 256) * 256L * 100 <= 115L * N));
+// The kernel vj_gemm_bf16 / vj_qkv_rope_gemm would run for a problem under the current VJ_GEMM_* knobs
+// (no device work; cus == 0: the current device's CU count). out6 = tile rows, tile columns, waves,
+// main-loop form (0 one tile / 1 staggered / 2 S64), workgroups per CU, tile group. Returns
+// VJ_ERR_UNSUPPORTED (out6 untouched) where the 256-row kernel declines.
+extern "C" int vj_gemm256_plan(int M, int N, int K, int a_kmajor, int b_kmajor, int epi, int cus, int* out6) {
+  VJ_CHECK_ARG(M > 0 && N > 0 && K > 0 && cus >= 0 && out6, "vj_gemm256_plan: bad arguments");
+  const Plan256 p = plan256(M, N, K, a_kmajor, b_kmajor, epi, cus ? cus : num_cus(), read_knobs());
+  if (!p.ok) return VJ_ERR_UNSUPPORTED;
+  const int v[6] = {p.bm, p.bn, p.waves, p.stg, p.per_cu, p.group};
+  memcpy(out6, v, sizeof(v));
+  return VJ_OK;
 }
 
 // Called by vj_gemm_bf16_splitk (splitk == 1) when the problem suits a 256-row tile; arguments
@@ -1528,51 +1347,21 @@ bool wide_tile_ok(int N) {
 int vj_gemm256_dispatch(int M, int N, int K, const void* A, long lda, int a_kmajor, const void* B, long ldb,
                         int b_kmajor, int epi, const float* bias, const void* aux, long ldaux, void* C, long ldc,
                         void* C2, long ldc2, hipStream_t st, const void* rope) {
-  if (epi < EPI_BF16 || (epi > EPI_ROPE && epi != EPI_BF16_RESID) || N % 8 || ldc % 4 || ldc2 % 4 || ldaux % 4)
-    return VJ_ERR_UNSUPPORTED;
+  if (ldc % 4 || ldc2 % 4 || ldaux % 4) return VJ_ERR_UNSUPPORTED;
   if (((uintptr_t)C & 15) || ((uintptr_t)C2 & 15) || ((uintptr_t)aux & 15) || ((uintptr_t)bias & 15))
     return VJ_ERR_UNSUPPORTED;
-  const int bn = wide_tile_ok(N) ? 256 : 128;  // direct-store epilogue on the 256-wide tiles
-  const int tm = vj_cdiv(M, 256), tn = vj_cdiv(N, bn);
+  const Knobs kn = read_knobs();
+  const Plan256 p = plan256(M, N, K, a_kmajor, b_kmajor, epi, num_cus(), kn);
+  if (!p.ok) return VJ_ERR_UNSUPPORTED;
   G256 g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, C, ldc, C2, ldc2, bias, aux, ldaux,
-         tm, tn, RopeP{}, K, 1, nullptr, tile_group(tm, tn)};
+         0, 0, RopeP{}, K, 1, nullptr, 0};
   if (epi == EPI_ROPE) {
     if (!rope) return VJ_ERR_UNSUPPORTED;
     g.rope = *(const RopeP*)rope;
     if (g.rope.hd % 4 || g.rope.D % 4 || g.rope.npos < 1 || g.rope.npos > 1024) return VJ_ERR_UNSUPPORTED;
     if ((long)g.rope.npos * g.rope.half > ROPE_TAB_MAX) return VJ_ERR_UNSUPPORTED;
   }
-  if (a_kmajor && b_kmajor && use_2w(bn == 128)) {
-    g.tiles_n = vj_cdiv(N, 128);
-    if (use_2w192(epi)) return launch2w192(epi, g, st);
-    return launch2w(epi, g, st);
-  }
-  if (bn == 256) {
-    // 192-row tiles run the one-tile main loop; where S64 can run instead (K % 64 == 0) the 256-row S64
-    // tiles measured +0.2 % per step over the cost model's 192-row picks (the context GEMMs;
-    // VJ_GEMM_BM192=0 vs default, two same-call runs each, profiles/r06_gemm_s64.txt).
-    // VJ_GEMM_BM192=1 still forces them.
-    const char* bm = getenv("VJ_GEMM_BM192");
-    const bool s64_ok = a_kmajor && b_kmajor && use_stg(K, epi) == 2 && !(bm && bm[0] == '1');
-    if (a_kmajor && b_kmajor && !s64_ok && use_bm192(M, tn)) {
-      g.tiles_m = vj_cdiv(M, 192);
-      g.group = tile_group(g.tiles_m, tn);
-      return launch192(epi, g, st);
-    }
-    if (a_kmajor && b_kmajor) {
-      const int form = use_stg(K, epi);
-      if (form == 2) return launch_stg<2>(epi, g, st);
-      if (form == 1) return launch_stg<1>(epi, g, st);
-    }
-    if (a_kmajor && b_kmajor) return launch256<true, true, 256>(epi, g, st);
-    if (a_kmajor && !b_kmajor) return launch256<true, false, 256>(epi, g, st);
-    if (!a_kmajor && b_kmajor) return launch256<false, true, 256>(epi, g, st);
-    return launch256<false, false, 256>(epi, g, st);
-  }
-  if (a_kmajor && b_kmajor) return launch256<true, true, 128>(epi, g, st);
-  if (a_kmajor && !b_kmajor) return launch256<true, false, 128>(epi, g, st);
-  if (!a_kmajor && b_kmajor) return launch256<false, true, 128>(epi, g, st);
-  return launch256<false, false, 128>(epi, g, st);
+  return launch_plan(p, a_kmajor, b_kmajor, epi, g, st, kn);
 }
 
 // Split-K partial products ws[z] = A[:, z-th K slice] B[z-th K slice, :]^T (f32, [splitk][M][N]) with
@@ -1581,16 +1370,13 @@ int vj_gemm256_dispatch(int M, int N, int K, const void* A, long lda, int a_kmaj
 int vj_gemm256_partial(int M, int N, int K, const void* A, long lda, int a_kmajor, const void* B, long ldb,
                        int b_kmajor, int kslice, int splitk, float* ws, hipStream_t st, float* rsum) {
   if (a_kmajor || b_kmajor || N % 8 || M < 256 || N < 128) return VJ_ERR_UNSUPPORTED;
-  // 256-wide tiles unless the last one would waste more than 15 % of the columns (the forward GEMMs'
-  // rule): ViT-g's N = 1408 runs 6 tiles of 256 instead of 11 of 128 (twice the work per operand byte)
-  const int bn = wide_tile_ok(N) ? 256 : 128;
-  const int tm = vj_cdiv(M, 256), tn = vj_cdiv(N, bn);
-  if ((long)tm * tn * splitk > 0x7fffffffL) return VJ_ERR_UNSUPPORTED;
+  const Knobs kn = read_knobs();
+  const Plan256 p{true, 256, wide_tile_ok(N) ? 256 : 128, 8, 0, 1, tile_group(kn)};
+  if ((long)vj_cdiv(M, p.bm) * vj_cdiv(N, p.bn) * splitk > 0x7fffffffL) return VJ_ERR_UNSUPPORTED;
   G256 g{(const bf16_t*)A, (const bf16_t*)B, M, N, K, lda, ldb, nullptr, 0, nullptr, 0, nullptr, nullptr, 0,
-         tm, tn, RopeP{}, kslice, splitk, ws, tile_group(tm, tn)};
+         0, 0, RopeP{}, kslice, splitk, ws, 0};
   g.rsum = rsum;
-  const int epi = rsum ? EPI_PARTIAL_RS : EPI_PARTIAL;
-  return bn == 256 ? launch256<false, false, 256>(epi, g, st) : launch256<false, false, 128>(epi, g, st);
+  return launch_plan(p, false, false, rsum ? EPI_PARTIAL_RS : EPI_PARTIAL, g, st, kn);
 }
 
 extern "C" int vj_gemm_bf16(int M, int N, int K, const void* A, long lda, int a_kmajor, const void* B, long ldb,
@@ -1645,10 +1431,9 @@ static int gemm256_f8(int M, int N, int K, const void* A, long lda, const int* e
   VJ_CHECK_ARG(epi == EPI_GELU || C, "vj_gemm_fp8: output C is required");
   VJ_CHECK_ARG((long)M * lda < 0x7fffffffL && (long)N * ldb < 0x7fffffffL, "vj_gemm_fp8: operand too large");
   // 256 x 128 tiles: the 256-wide fp8 tile needs ~20 VGPRs more than the bf16 one and spills
-  const int bn = 128;
-  const int tm = vj_cdiv(M, 256), tn = vj_cdiv(N, bn);
+  const Knobs kn = read_knobs();
   G256 g{(const bf16_t*)A, (const bf16_t*)B, M, N, K / 2, lda / 2, ldb / 2, C, ldc, C2, ldc2, bias, aux, ldaux,
-         tm, tn, RopeP{}, K / 2, 1, nullptr, tile_group(tm, tn), ea, eb};
+         vj_cdiv(M, 256), vj_cdiv(N, 128), RopeP{}, K / 2, 1, nullptr, tile_group(kn), ea, eb};
   if (epi == EPI_ROPE) {
     VJ_CHECK_ARG(rope != nullptr, "vj_gemm_fp8: EPI_ROPE needs the rope tables");
     g.rope = *rope;
@@ -1656,7 +1441,7 @@ static int gemm256_f8(int M, int N, int K, const void* A, long lda, const int* e
                      (long)g.rope.npos * g.rope.half <= ROPE_TAB_MAX,
                  "vj_gemm_fp8: rope table too large (npos=%d)", g.rope.npos);
   }
-  return launch256_f8<128>(epi, g, st);
+  return launch256<true, true, 128, true>(epi, g, st, kn);
 }
 
 extern "C" int vj_gemm_fp8(int M, int N, int K, const void* A, long lda, const int* ea, const void* B, long ldb,

@@ -1,6 +1,6 @@
 // Device helpers of the 256-row bf16 / fp8 GEMM kernel (vj_gemm256.hip): the kernel argument block, LDS-DMA
-// staging of K-major / MN-major operand tiles with the XOR swizzles, MFMA fragment reads and the
-// GELU epilogue pair. Everything sits in an anonymous namespace: each translation unit compiles
+// staging of K-major / MN-major operand tiles with the XOR swizzles, MFMA fragment reads, the
+// GELU epilogue pair and Cfg256, the kernel's compile-time configuration (geometry, LDS layout). Everything sits in an anonymous namespace: each translation unit compiles
 // its own copy (no cross-TU codegen coupling of the kernels).
 #pragma once
 #include "vj_common.h"
@@ -194,6 +194,150 @@ __device__ __forceinline__ uint32_t gelu_pair_tab(uint32_t pk, const LDS_AS char
 
 struct Tile {
   int m0, n0, z, Keff, nk;  // buffer descriptors are rebuilt per DMA: SGPRs are the scarce resource
+};
+
+// bf16 -> f32 of the low / high half of a packed pair (exact)
+__device__ __forceinline__ float bf_lo(uint32_t u) { return __builtin_bit_cast(float, u << 16); }
+__device__ __forceinline__ float bf_hi(uint32_t u) { return __builtin_bit_cast(float, u & 0xffff0000u); }
+// the same on a pair held in a float register (the bit pattern of a 4-byte load)
+__device__ __forceinline__ float bf_lo(float u) { return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, u) << 16); }
+__device__ __forceinline__ float bf_hi(float u) {
+  return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, u) & 0xffff0000u);
+}
+
+// Schedule choices fixed by round-3 measurements (the variants were removed from the source; the
+// numbers are in DESIGN.md and profiles/r03_gemm_*):
+//  * 8-wave main loop: only the A pieces of K-tile t + 2 go out after the barrier; the B pieces are
+//    issued after 3 of the last phase's 4 m-tiles (SPLIT_AT): -2..-7 % and a further 0..-5 % on the
+//    ViT-L shapes (r03_gemm_spread_kernels.txt,
+//    r03_gemm_split_kernels.txt). Also the A pieces after the first m-tile: slower.
+//  * on 256-wide bf16 tiles without a VALU-heavy epilogue only waves 0-3 issue the main-loop LDS-DMA
+//    (DMA_WAVES; their SIMD partners keep issuing MFMAs); the next tile's stage 1, issued around the
+//    epilogue, goes out from all 8 waves (r03_gemm_dmaw4_kernels.txt, r03_gemm_s1all_step_ab.txt).
+//    Slower and removed: the RoPE / GELU tiles on 4 DMA waves, A / B pieces split over waves 0-3 /
+//    4-7, the DMA from waves 4-7, s_setprio around the MFMA clusters or for waves 4-7.
+//  * one m-tile of residual / saved-derivative rows prefetched ahead in the direct epilogue (deeper:
+//    no faster, r03 stamps).
+constexpr int SPLIT_AT = 3;
+constexpr int DMA_WAVES = 4;
+constexpr int AUX_PF = 1;
+
+constexpr int LDS_PER_CU = 163840;
+constexpr int cmax(int a, int b) { return a > b ? a : b; }
+
+// Everything k_gemm256<AK, BKM, EPI, BN, F8, NWV, BMT, STG> derives from its template parameters: which
+// combinations exist (`supported`: the kernel asserts it, the launcher instantiates nothing else), the
+// tile / wave geometry, the schedule switches, the launch shape and the LDS layout. LDS_BYTES is the
+// end of the furthest region, so a region cannot outgrow the array unnoticed.
+//
+// NWV = 8: 8 waves (2 x 4), 64-deep K tiles, one workgroup per CU. NWV = 4 ("2W"): 4 waves (2 x 2),
+// TWO workgroups per CU, so one workgroup's epilogue (HBM / VALU) runs under the other's main loop
+// (MFMA); K-major operands only; 192 x 128 tiles 64 deep (80 KB, the default) or 256 x 128 tiles 32
+// deep (64 KB with the RoPE table area).
+// BMT = 192 (K-major bf16 direct-store tiles only): 96-row wave tiles (3 m-tiles per M-half) for
+// problems whose 256-row tile count leaves a round of CUs under-filled (context GEMMs, M ~ 11.7k:
+// 184 tiles of 256 x 256 on 256 CUs -> 244 tiles of 192 x 256).
+// STG: the staggered main loops (vj_gemm256.hip), 1 = 32-deep units, 2 = S64.
+template <bool AK, bool BKM, int EPI, int BN, bool F8, int NWV, int BMT, int STG>
+struct Cfg256 {
+  static constexpr bool PART = EPI == EPI_PARTIAL || EPI == EPI_PARTIAL_RS;  // split-K partial slabs (RS: + row sums)
+  static constexpr bool RS = EPI == EPI_PARTIAL_RS;
+  static constexpr int BM = BMT;
+  static constexpr int MH = BM / 64;  // virtual 16-row m-tiles per half of the wave's rows (4 / 3)
+  // 2-workgroup kernels: 256 x 128 tiles 32 deep (64-B LDS rows), or 192 x 128 tiles 64 deep (128-B
+  // rows: whole cache lines per DMA piece, half the L1 -> L2 requests; 80 KB, no table: RoPE excluded)
+  static constexpr int BK = (NWV == 8 || BMT == 192) ? 64 : 32;
+  static constexpr int NT = NWV * 64;
+  static constexpr int WNX = NWV / 2;    // waves across N (4 / 2)
+  static constexpr int WMX = NWV / WNX;  // waves across M (2)
+  static constexpr int WM = BM / WMX;    // wave tile rows (128 / 96)
+  static constexpr int WN = BN / WNX;    // wave tile columns (64 / 32)
+  static constexpr int PB = 16;          // MFMA output block width
+  static constexpr int NTN = WN / PB;    // n blocks per wave (4 / 2)
+  static constexpr int A_BYTES = BM * BK * 2;
+  static constexpr int B_BYTES = BN * BK * 2;
+  static constexpr int STAGE = A_BYTES + B_BYTES;
+  // LDS-DMA issuers: DMA_WAVES = 4 -> waves 0-3 only on 256-wide tiles (their SIMD partners 4-7 keep
+  // issuing MFMAs meanwhile), except the RoPE / GELU / GELU-backward tiles, whose next-tile stage 1
+  // goes out right before (or in) their VALU-heavy epilogue, where waves 0-3 would start it 16
+  // pieces late; 128-wide tiles (the predictor's N = 384) measured slower with it.
+  static constexpr bool VALU_EPI = EPI == EPI_ROPE || EPI == EPI_GELU || EPI == EPI_GELU_BWD;
+  static constexpr int DMAW = NWV != 8 ? NWV : (VALU_EPI || BN != 256 || F8) ? 8 : DMA_WAVES;
+  // K-major B with 4 n blocks per wave: permuted B staging + stores straight from registers (16-B
+  // f32 / 8-B bf16 per row); 128-wide tiles would store 4-8 B per lane, so they keep the LDS path
+  static constexpr bool DIRECT = BKM && NTN == 4;
+  static constexpr bool AUX = EPI == EPI_F32_RESID || EPI == EPI_GELU_BWD || EPI == EPI_BF16_RESID;
+  static constexpr bool F32OUT = EPI == EPI_F32 || EPI == EPI_F32_RESID || PART;
+  // MN-major operands are read with asm transposed reads (ds_read_tr16_async)
+  static constexpr bool ASYNC = !AK || !BKM;
+  // The next tile's stage 0 is DMA'd during this tile's last K-tile. Its stage 1 goes out right
+  // after the last barrier, unless the epilogue still needs that LDS slot (staged epilogue: after
+  // it) or issues global loads that would queue behind the DMA in vmcnt order (AUX: once the last
+  // aux rows are fetched).
+  static constexpr bool EARLY1 = DIRECT && !AUX;
+
+  static constexpr bool supported =
+      // staggered main loops: 8-wave K-major bf16 256 x 256 tiles
+      (!STG || (AK && BKM && !F8 && NWV == 8 && BMT == 256 && BN == 256 && !PART)) &&
+      // fp8: the forward epilogues only
+      (!F8 || (AK && BKM && (EPI == EPI_BF16 || EPI == EPI_F32 || EPI == EPI_F32_RESID || EPI == EPI_GELU ||
+                             EPI == EPI_ROPE))) &&
+      // 2-workgroup GEMM: K-major bf16 operands only
+      (NWV == 8 || (NWV == 4 && AK && BKM && !F8)) &&
+      // 192-row tiles: direct K-major bf16 (the 4-wave kernel without the RoPE table)
+      (BMT == 256 || (BMT == 192 && !F8 && AK && DIRECT && (NWV == 8 || EPI != EPI_ROPE))) &&
+      // bf16 residual: forward GEMMs (both K-major); split-K slabs: weight gradients (both MN-major)
+      (EPI != EPI_BF16_RESID || (AK && BKM)) && (!PART || (!AK && !BKM));
+
+  // STG: ring of NSL 32-KB unit slots, DMA distance NSL - 2 units; 5 slots (all 160 KB of the CU's
+  // LDS, distance 3) unless the RoPE epilogue needs the table area (4 slots + table, distance 2)
+  // (GTAB: the GELU epilogue by table, 4 slots behind the 28.7-KB table at LDS offset 0, whose byte
+  // offsets then fit the 16-bit lanes the lookup computes them in). More slots than 4 (distance 2,
+  // the depth of the RoPE / GELU kernels) measured the same on every target shape: DESIGN.md.
+  static constexpr bool GTAB = STG && EPI == EPI_GELU;
+  static constexpr int USZ = 32768;
+  static constexpr int NSL = STG ? ((EPI == EPI_ROPE || GTAB) ? 4 : 5) : 1;
+  static constexpr int DIST = NSL - 2;
+  // S64 (STG == 2): the same ring area as 16-KB granules, SA A slots then SB B slots (DMA distance
+  // SA - 1 / SB - 1 granules). 4 + 4 granules = the 4-slot ring's 128 KB, beside the GELU / RoPE tables.
+  // Deeper B rings (5 / 6 on the kernels without an LDS table) removed the DMA stalls of a tile's
+  // first K steps (interval stamps) but slowed every later step: qkv tgt 260 -> 274 us, step -0.6 %
+  // (profiles/r06_gemm_s64.txt); 4 kept.
+  static constexpr bool S64 = STG == 2;
+  static constexpr int GSZ = 16384;
+  static constexpr int SA = 4, SB = 4;
+  static constexpr int EA = SA - 1, EB = SB - 1;
+  // first row of the wave's rows (S64: the wave's 64-row band in each 128-row half)
+  static constexpr int WRS = S64 ? 64 : WM;
+
+  // staged epilogue (!DIRECT): passes of MTP m-tiles (16 * MTP rows) per wave through a padded image in
+  // the last K-tile's operand slot: 2 m-tiles per pass where the image fits the slot (BN = 128), else 1
+  static constexpr int STR = WN + 4;    // floats per staged row (conflict-free ds_write_b32)
+  static constexpr int LPR = WN / 4;    // lanes per staged row (16-B each)
+  static constexpr int RPI = 64 / LPR;  // rows per wave-instruction
+  static constexpr int MTP = (NWV * 32 * STR * 4 <= STAGE) ? 2 : 1;
+  static constexpr int PR = 16 * MTP;   // rows per pass
+  static constexpr int IT = PR / RPI;   // row-instructions per pass
+
+  // ---- LDS regions (byte offset, size). One-tile kernels: two operand slots, then the table area
+  // (every epilogue reserves it; 2 x 80 KB of the 4-wave 192-row kernel leave no room: RoPE excluded).
+  // Staggered kernels: [GELU table] ring [RoPE table area].
+  static constexpr int SLOT_OFF = 0, SLOT_END = STG ? 0 : 2 * STAGE;
+  static constexpr int GTAB_OFF = 0, GTAB_END = GTAB ? GT_BYTES : 0;
+  static constexpr int RING0 = GTAB ? 32768 : 0, RING_END = STG ? RING0 + NSL * USZ : 0;
+  static constexpr int S64_END = S64 ? RING0 + (SA + SB) * GSZ : 0;  // the granule rings, inside the ring area
+  static constexpr int TABB = (STG ? EPI != EPI_ROPE : (NWV == 4 && BMT == 192)) ? 0 : TAB_BYTES;
+  static constexpr int TAB_OFF = 2 * STAGE, TAB_END = TABB ? TAB_OFF + TABB : 0;
+  // RoPE: tile-row positions (frame | row << 10 | col << 20), then the interleaved cos/sin table
+  static constexpr int RPOS_OFF = TAB_OFF, RTAB_OFF = RPOS_OFF + BM * 4;
+  static constexpr int RTAB_END = EPI == EPI_ROPE ? RTAB_OFF + ROPE_TAB_MAX * 8 : 0;
+  static constexpr int IMG_END = DIRECT ? 0 : STAGE + NWV * PR * STR * 4;  // image in the second slot
+  static constexpr int LDS_BYTES = cmax(cmax(SLOT_END, RING_END), TAB_END);
+  static constexpr int THREADS = NT;
+  static constexpr int BLOCKS_PER_CU = NWV == 4 ? 2 : 1;
+  // regions that must not overlap: table | ring | table area, operand slots | table area
+  static constexpr bool lds_disjoint = GTAB_END <= RING0 && (TABB == 0 || cmax(SLOT_END, RING_END) <= TAB_OFF) &&
+                                       (EPI != EPI_ROPE || RTAB_END <= TAB_END);
 };
 
 }  // namespace

@@ -115,6 +115,12 @@ def _effective_splitk(K, splitk):
     return (K + kslice - 1) // kslice
 
 
+def wgrad_wide_tile(N):
+    """The C side's column-tile rule (vj_gemm256.hip wide_tile_ok), restated here so that sizing a split
+    costs no library call; tests/test_capi.py holds the two together through vj_gemm256_plan."""
+    return N % 256 == 0 or (N > 256 and -(-N // 256) * 256 * 100 <= 115 * N)
+
+
 def wgrad_splitk(M, N, K, cus=None):
     """Split K (tokens) of a weight-gradient GEMM [M, N] += A[M, K] B[K, N]. Tiles are 256 x (256 or
     128) when M >= 256 and N >= 128 (the C side's choice), else 128 x 128. Picks the split that
@@ -128,9 +134,8 @@ def wgrad_splitk(M, N, K, cus=None):
     stream configuration (tests/test_gpu_production.py)."""
     if cus is None:
         cus = 256
-    if M >= 256 and N >= 128:  # the C side's column-tile rule (vj_gemm256.hip wide_tile_ok)
-        wide = N % 256 == 0 or (N > 256 and -(-N // 256) * 256 * 100 <= 115 * N)
-        tm, tn, per_cu = 256, (256 if wide else 128), 1
+    if M >= 256 and N >= 128:
+        tm, tn, per_cu = 256, (256 if wgrad_wide_tile(N) else 128), 1
     else:
         tm, tn, per_cu = 128, 128, 2
     tiles = -(-M // tm) * -(-N // tn)
