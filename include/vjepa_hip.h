@@ -307,6 +307,19 @@ int vj_xattn_bwd(int B, int nq, int N, int H, int hd, const void* q, long ldq, c
                  const void* o, long ldo, const void* dout, long lddo, const float* lse2, float scale, void* dq,
                  long lddq, void* dkv, long lddkv, float* ws, long ws_floats, void* stream);
 
+/* Fused multi-view softmax cross-entropy of the frozen-encoder probe, one classifier head per call
+ * (evals/video_classification_frozen/eval.py:299, 325-328: torch.nn.CrossEntropyLoss() per view, the
+ * view-averaged F.softmax, .max(dim=1).indices.eq(labels).sum()). logits f32 [V*B][ld], row v*B + b =
+ * sample b of view v; labels [B] int64 (labels_i64 != 0) or int32. Outputs: loss f32 [V] (per view, mean
+ * over b of logsumexp(row) - row[label]), row_loss f32 [V*B], dlogits f32 [V*B][lddl] or NULL (validation)
+ * = (softmax(row) - onehot(label)) / B, the gradient of the SUM of the V view losses (eval.py:335/339),
+ * pred int32 [B] = argmax_c of sum_v softmax(row v*B + b)[c] (lowest index on an exact tie), correct
+ * int32 [1] = #{b : pred[b] == labels[b]}. f32 math with the row maximum subtracted; only columns
+ * [0, C) of a row are read or written. A label outside [0, C) indexes nothing and matches no class: the
+ * row's loss is its log-sum-exp, its gradient softmax / B (no ignore_index). V, B, C >= 1, ld >= C. */
+int vj_xent(int V, int B, int C, const float* logits, long ld, const void* labels, int labels_i64, float* loss,
+            float* row_loss, float* dlogits, long lddl, int* pred, int* correct, void* stream);
+
 /* fp32-operand parity mode (vj_f32.hip): the encoder forward with f32 operands throughout, to show
  * the bf16 path's distance from the fp32 reference is operand rounding only. Not on the training
  * path. vj_gemm_f32: C = A B^T + bias (+ resid), epi as vj_gemm_bf16 (F32 = 1, F32_RESID = 2,

@@ -689,6 +689,55 @@ def jepa_loss(z, tgt, loss_rows, gamma, beta, group_rows, eps1=1e-6, eps2=1e-5, 
     return loss, dz, row_loss
 
 
+def xent(logits, labels, views=1, want_grad=True, out=None):
+    """Fused multi-view softmax cross-entropy of one probe head (vj_xent; eval.py:299, 325-328).
+
+    logits f32 [V*B, C] (row v*B + b = sample b of view v, row stride >= C), labels [B] int64 or int32.
+    Returns (loss f32 [V], row_loss f32 [V*B], dlogits f32 [V*B, C] or None, pred int32 [B], correct
+    int32 [1]): loss[v] is CrossEntropyLoss() (mean reduction, defaults) of view v, dlogits the gradient
+    of the sum of the V losses, pred the argmax of the view-averaged softmax, correct the top-1 count.
+    want_grad=False (validation) skips dlogits. out: an optional (loss, row_loss, dlogits, pred, correct)
+    tuple of preallocated buffers (dlogits may have a row stride > C).
+
+    ignore_index is NOT supported (the reference's CrossEntropyLoss default -100 never occurs in its
+    loaders): CPU labels outside [0, C) raise IndexError as F.cross_entropy would; device labels are
+    not read back (no host sync) unless VJ_CHECK_INDICES=1, and the kernel treats such a row as
+    "no class matches" (loss = log-sum-exp, gradient = softmax / B) without indexing memory."""
+    _dev(logits)
+    assert logits.dtype == F32 and labels.dtype in (torch.int64, torch.int32)
+    ld = _rowmajor(logits, "logits")
+    R, C = logits.shape
+    V = int(views)
+    if labels.dim() != 1 or V < 1 or R % V != 0 or labels.numel() != R // V:
+        raise ValueError(f"xent: logits {tuple(logits.shape)} are not {V} views of {labels.numel()} labels")
+    B = R // V
+    if B and (not labels.is_cuda or os.environ.get("VJ_CHECK_INDICES", "0") == "1"):
+        lo, hi = int(labels.min()), int(labels.max())
+        if lo < 0 or hi >= C:
+            raise IndexError(f"xent: label {hi if hi >= C else lo} out of range for {C} classes")
+    labels = labels.to(logits.device).contiguous()
+    if out is None:
+        dev = logits.device
+        out = (torch.empty(V, dtype=F32, device=dev), torch.empty(R, dtype=F32, device=dev),
+               torch.empty(R, C, dtype=F32, device=dev) if want_grad else None,
+               torch.empty(B, dtype=torch.int32, device=dev), torch.empty(1, dtype=torch.int32, device=dev))
+    loss, row_loss, dl, pred, correct = out
+    if not want_grad:
+        dl = None
+    _dev(loss, row_loss, dl, pred, correct)
+    assert loss.dtype == F32 and loss.numel() >= V and loss.is_contiguous()
+    assert row_loss.dtype == F32 and row_loss.numel() >= R and row_loss.is_contiguous()
+    assert pred.dtype == torch.int32 and pred.numel() >= B and pred.is_contiguous()
+    assert correct.dtype == torch.int32 and correct.numel() >= 1
+    lddl = 0
+    if dl is not None:
+        assert dl.dtype == F32 and tuple(dl.shape) == (R, C)
+        lddl = _rowmajor(dl, "dlogits")
+    _call("vj_xent", V, B, C, _p(logits), ld, _p(labels), int(labels.dtype == torch.int64), _p(loss), _p(row_loss),
+          _p(dl), lddl, _p(pred), _p(correct), _stream())
+    return loss, row_loss, dl, pred, correct
+
+
 def check_finite(g, found_inf):
     _dev(g, found_inf)
     _call("vj_check_finite", g.numel(), _p(g), _p(found_inf), _stream())

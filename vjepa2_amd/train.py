@@ -18,6 +18,7 @@ change no numerics, so the config key is accepted and ignored.
 import copy
 import csv
 import logging
+import math
 import os
 import time
 
@@ -334,6 +335,32 @@ class SyntheticVideoDataset(torch.utils.data.Dataset):
         g = torch.Generator().manual_seed(self.seed_offset + i)
         clip = torch.randn(3, self.fpc, self.crop, self.crop, generator=g)
         return [clip], 0, [torch.arange(self.fpc)]
+
+
+class SyntheticLabelledVideoDataset(torch.utils.data.Dataset):
+    """Labelled multi-segment, multi-view samples in the layout the frozen-encoder evals' loaders deliver
+    (evals/video_classification_frozen/eval.py:308-313): (clips, label, clip_indices) with clips a list
+    over segments of lists over views of [3, F, S, S] and clip_indices a list over segments of the
+    segment's F frame indices; the default collate batches every leaf. Deterministic per index."""
+
+    def __init__(self, num_samples, frames_per_clip, crop_size, num_classes, num_segments=1, num_views=1,
+                 seed_offset=0):
+        self.n, self.fpc, self.crop, self.classes = num_samples, frames_per_clip, crop_size, num_classes
+        self.segments, self.views, self.seed_offset = num_segments, num_views, seed_offset
+        self.labels = (torch.arange(num_samples) * 7 + 3 + seed_offset) % num_classes
+
+    def __len__(self):
+        return self.n
+
+    def __getitem__(self, i):
+        g = torch.Generator().manual_seed(self.seed_offset + 2000 + i)
+        label = int(self.labels[i])
+        # a faint label-dependent offset: a probe can learn it, the clips stay unit-scale noise
+        shift = 0.5 * math.sin(1.0 + label)
+        clips = [[torch.randn(3, self.fpc, self.crop, self.crop, generator=g) + shift for _ in range(self.views)]
+                 for _ in range(self.segments)]
+        indices = [torch.arange(self.fpc) + s * self.fpc for s in range(self.segments)]
+        return clips, label, indices
 
 
 def init_data(batch_size, collator, dataset_fpcs, crop_size, rank=0, world_size=1, num_workers=0, num_samples=None,
