@@ -72,7 +72,8 @@ int vj_gemm_bf16_wgrad(int M, int N, int K, const void* dy, long lddy, const voi
  * MFMA loops; F.scaled_dot_product_attention,
  * modules.py:367-372 / 411-418). Tokens of `ngroups` groups of equal-length sequences are
  * concatenated: group g has nseq[g] sequences of len[g] tokens. q/k/v at columns q_off/k_off/v_off
- * + h*hd of the [T, ld] bf16 buffer; O bf16 [T, ldo] at column h*hd.
+ * + h*hd of the [T, ld] bf16 buffer; O bf16 [T, ldo] at column h*hd. Rows are moved in 16-B pieces:
+ * ld, ldo (backward: lddo, ldd) and the three offsets are multiples of 8, the offsets non-negative.
  * stats: f32 [2][H][T]; forward writes stats[0] = log2-sum-exp2 of the scaled scores in base-2 units
  * (= logsumexp(scale * s) * log2(e)) per (head, token). */
 int vj_attn_fwd(int T, int H, int hd, const void* qkv, long ld, int q_off, int k_off, int v_off, void* o, long ldo,

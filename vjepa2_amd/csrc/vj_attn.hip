@@ -997,11 +997,15 @@ int fill_groups(SeqGroups& sg, int ngroups, const int* nseq, const int* len, int
   return VJ_OK;
 }
 
-int check_common(int H, int hd, long ld, long ldo) {
+int check_common(int H, int hd, long ld, long ldo, int q_off, int k_off, int v_off) {
   VJ_CHECK_ARG(hd == 64 || hd == 32 || hd == 80 || hd == 88,
                "attention: head_dim must be 32, 64, 80 or 88 (got %d)", hd);
   VJ_CHECK_ARG(H >= 1 && H <= 65535, "attention: bad H=%d", H);
   VJ_CHECK_ARG(ld % 8 == 0 && ldo % 8 == 0, "attention: row strides must be multiples of 8");
+  // q / k / v rows are read (and dq / dk / dv rows stored) in 16-B pieces from column off + h * hd
+  VJ_CHECK_ARG(q_off >= 0 && k_off >= 0 && v_off >= 0 && q_off % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0,
+               "attention: q / k / v column offsets must be non-negative multiples of 8 (got %d, %d, %d)", q_off,
+               k_off, v_off);
   return VJ_OK;
 }
 
@@ -1014,7 +1018,7 @@ extern "C" int vj_attn_fwd_ex(int T, int H, int hd, const void* qkv, long ld, in
                               void* o, long ldo, float* lse_stats, float scale, int ngroups, const int* nseq,
                               const int* len, int fblk, float dropout_p, unsigned seed, void* stream) {
   if (T == 0) return VJ_OK;
-  int rc = check_common(H, hd, ld, ldo);
+  int rc = check_common(H, hd, ld, ldo, q_off, k_off, v_off);
   if (rc) return rc;
   VJ_CHECK_ARG(fblk >= 0, "vj_attn_fwd: bad frame block %d", fblk);
   VJ_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "vj_attn_fwd: dropout_p must be in [0, 1)");
@@ -1062,7 +1066,7 @@ extern "C" int vj_attn_bwd_ex(int T, int H, int hd, const void* qkv, long ld, in
                               const int* rope_ids, int rope_mod, int rope_tpf, int rope_tpr, const float* cos_t,
                               const float* sin_t, int fblk, float dropout_p, unsigned seed, void* stream) {
   if (T == 0) return VJ_OK;
-  int rc = check_common(H, hd, ld, ldo);
+  int rc = check_common(H, hd, ld, ldo, q_off, k_off, v_off);
   if (rc) return rc;
   VJ_CHECK_ARG(fblk >= 0, "vj_attn_bwd: bad frame block %d", fblk);
   VJ_CHECK_ARG(dropout_p >= 0.f && dropout_p < 1.f, "vj_attn_bwd: dropout_p must be in [0, 1)");
