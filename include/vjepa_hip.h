@@ -321,6 +321,27 @@ int vj_xattn_bwd(int B, int nq, int N, int H, int hd, const void* q, long ldq, c
 int vj_xent(int V, int B, int C, const float* logits, long ld, const void* labels, int labels_i64, float* loss,
             float* row_loss, float* dlogits, long lddl, int* pred, int* correct, void* stream);
 
+/* Fused sigmoid focal loss, its gradient and the top-k class-recall bookkeeping of the frozen
+ * action-anticipation probe, up to three heads of one classifier per call
+ * (evals/action_anticipation_frozen/losses.py:9-49 with reduction="sum", metrics.py:19-42).
+ * logits, ld, C, labels, valid, dlogits, lddl, tp, fn are HOST arrays of nseg (1..3) entries, read before the
+ * call returns. Segment s: logits[s] f32 [B][ld[s]] (ld >= C: segments may be column slices of one buffer),
+ * labels[s] [B] int64 (labels_i64 != 0) or int32, valid[s] bytes [C[s]] (non-zero = valid class) or NULL = all
+ * valid (valid itself may be NULL), dlogits[s] f32 [B][lddl[s]] or NULL (dlogits itself may be NULL), tp[s] /
+ * fn[s] int32 [C[s]] counters that are ACCUMULATED into. loss_kind 1: loss f32 [nseg] = sum over B * C of
+ * alpha_t * BCEWithLogits(x, t) * (1 - p_t)^gamma (alpha_t only if alpha >= 0), dlogits its gradient;
+ * row_loss f32 [nseg * B] is workspace (the row sums). loss_kind 0: metrics only, loss / row_loss / dlogits
+ * are not touched (may be NULL). hit int32 [nseg * B]: row b of segment s is a hit iff
+ *   rank = #{valid c : x_c > x_label} + #{valid c < label : x_c == x_label} < k
+ * (label's class invalid: every valid class counts as greater, invalid classes of a lower index as ties; a
+ * NaN is not greater; ties: the lower class index ranks first). A hit adds 1 to tp[label], a miss to
+ * fn[label]. A label outside [0, C) matches no class, indexes nothing, updates no counter, hit = 0. Float
+ * sums are fixed-order (bitwise reproducible); only the integer counters use atomics. */
+int vj_focal(int B, int nseg, const float* const* logits, const long* ld, const int* C, const void* const* labels,
+             int labels_i64, const unsigned char* const* valid, float* const* dlogits, const long* lddl,
+             int* const* tp, int* const* fn, float alpha, float gamma, int k, int loss_kind, float* loss,
+             float* row_loss, int* hit, void* stream);
+
 /* fp32-operand parity mode (vj_f32.hip): the encoder forward with f32 operands throughout, to show
  * the bf16 path's distance from the fp32 reference is operand rounding only. Not on the training
  * path. vj_gemm_f32: C = A B^T + bias (+ resid), epi as vj_gemm_bf16 (F32 = 1, F32_RESID = 2,

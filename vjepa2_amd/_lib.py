@@ -82,6 +82,7 @@ SIGNATURES = {
     "vj_xattn_fwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _F, _P, _L, _P],
     "vj_xattn_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _F, _P, _L, _P, _L, _P, _L, _P],
     "vj_xent": [_I, _I, _I, _P, _L, _P, _I, _P, _P, _P, _L, _P, _P, _P],
+    "vj_focal": [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P],
 }
 
 _lib = None

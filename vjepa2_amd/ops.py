@@ -4,6 +4,7 @@ Every function validates shapes/dtypes/devices on the host (so a kernel never se
 was not written for), then enqueues the kernel on torch's current HIP stream. No CPU fallback.
 """
 
+import ctypes
 import os
 
 import torch
@@ -736,6 +737,88 @@ def xent(logits, labels, views=1, want_grad=True, out=None):
     _call("vj_xent", V, B, C, _p(logits), ld, _p(labels), int(labels.dtype == torch.int64), _p(loss), _p(row_loss),
           _p(dl), lddl, _p(pred), _p(correct), _stream())
     return loss, row_loss, dl, pred, correct
+
+
+def focal(logits, labels, tp, fn, valid=None, alpha=0.25, gamma=2.0, k=5, loss_kind=1, want_grad=True, out=None):
+    """Fused sigmoid focal loss + gradient + top-k class-recall counters of one anticipation classifier
+    (vj_focal; evals/action_anticipation_frozen/losses.py:9-49 with reduction="sum", metrics.py:19-42).
+
+    logits, labels, tp, fn (and valid, if given): sequences of 1..3 entries, one per head. logits[s] f32
+    [B, C_s] (row stride >= C_s: heads may be column slices of one buffer), labels[s] [B] int64 or int32 (one
+    dtype for all heads), tp[s] / fn[s] int32 [C_s] device counters that are accumulated into, valid[s] a
+    bool / uint8 [C_s] device mask of the classes that count for the ranking, or None (all of them).
+    Returns (loss f32 [nseg], dlogits list of f32 [B, C_s] or None, hit int32 [nseg, B]): loss[s] the summed
+    focal loss of head s, dlogits[s] its gradient, hit[s, b] whether label b is among the top k of its row
+    (rank count; among equal logits the lower class index ranks first). loss_kind=0 computes the metrics
+    only (loss and dlogits are None), want_grad=False skips dlogits. out: an optional (loss, row_loss,
+    dlogits, hit) tuple of preallocated buffers (row_loss f32 [nseg * B] workspace; dlogits a list whose
+    tensors may have a row stride > C_s, or None).
+
+    CPU labels outside [0, C_s) raise IndexError; device labels are not read back (no host sync) unless
+    VJ_CHECK_INDICES=1, and the kernel gives such a row no target class and no counter update."""
+    logits, labels, tp, fn = list(logits), list(labels), list(tp), list(fn)
+    nseg = len(logits)
+    if not 1 <= nseg <= 3 or not (len(labels) == len(tp) == len(fn) == nseg):
+        raise ValueError(f"focal: 1..3 heads with labels, tp and fn each (got {nseg}, {len(labels)}, {len(tp)}, "
+                         f"{len(fn)})")
+    valid = [None] * nseg if valid is None else list(valid)
+    if len(valid) != nseg:
+        raise ValueError(f"focal: {len(valid)} valid masks for {nseg} heads")
+    _dev(*logits, *tp, *fn, *valid)
+    if loss_kind not in (0, 1):
+        raise ValueError(f"focal: loss_kind {loss_kind} (0 = metrics only, 1 = focal)")
+    B = logits[0].shape[0] if logits[0].dim() == 2 else -1
+    dev = logits[0].device
+    lds, Cs, lab_dev, val_dev = [], [], [], []
+    for s in range(nseg):
+        x, lb = logits[s], labels[s]
+        assert x.dtype == F32 and lb.dtype == labels[0].dtype and lb.dtype in (torch.int64, torch.int32)
+        lds.append(_rowmajor(x, f"logits[{s}]"))
+        C = x.shape[1]
+        if x.shape[0] != B or B < 1 or C < 1 or lb.dim() != 1 or lb.numel() != B:
+            raise ValueError(f"focal: head {s} logits {tuple(x.shape)} / labels {tuple(lb.shape)} do not match "
+                             f"{B} rows")
+        if not lb.is_cuda or os.environ.get("VJ_CHECK_INDICES", "0") == "1":
+            lo, hi = int(lb.min()), int(lb.max())
+            if lo < 0 or hi >= C:
+                raise IndexError(f"focal: head {s} label {hi if hi >= C else lo} out of range for {C} classes")
+        for name, t in (("tp", tp[s]), ("fn", fn[s])):
+            if t.dtype != torch.int32 or t.numel() != C or not t.is_contiguous():
+                raise ValueError(f"focal: {name}[{s}] must be a contiguous int32 [{C}] tensor")
+        v = valid[s]
+        if v is not None:
+            if v.dtype not in (torch.bool, torch.uint8) or v.numel() != C or not v.is_contiguous():
+                raise ValueError(f"focal: valid[{s}] must be a contiguous bool / uint8 [{C}] tensor")
+        Cs.append(C)
+        lab_dev.append(lb.to(dev).contiguous())
+        val_dev.append(v)
+    want_grad = bool(want_grad and loss_kind)
+    if out is None:
+        out = (torch.empty(nseg, dtype=F32, device=dev) if loss_kind else None,
+               torch.empty(nseg * B, dtype=F32, device=dev) if loss_kind else None,
+               [torch.empty(B, C, dtype=F32, device=dev) for C in Cs] if want_grad else None,
+               torch.empty(nseg, B, dtype=torch.int32, device=dev))
+    loss, row_loss, dls, hit = out
+    if not want_grad and loss_kind:
+        dls = None
+    _dev(loss, row_loss, hit, *(dls or []))
+    assert hit.dtype == torch.int32 and hit.numel() >= nseg * B and hit.is_contiguous()
+    if loss_kind:
+        assert loss.dtype == F32 and loss.numel() >= nseg and loss.is_contiguous()
+        assert row_loss.dtype == F32 and row_loss.numel() >= nseg * B and row_loss.is_contiguous()
+    lddls = [0] * nseg
+    if dls is not None:
+        dls = list(dls)
+        assert len(dls) == nseg
+        for s, d in enumerate(dls):
+            assert d.dtype == F32 and tuple(d.shape) == (B, Cs[s])
+            lddls[s] = _rowmajor(d, f"dlogits[{s}]")
+    ptrs = lambda ts: (ctypes.c_void_p * nseg)(*[_p(t) for t in ts])  # noqa: E731
+    _call("vj_focal", B, nseg, ptrs(logits), (ctypes.c_long * nseg)(*lds), (ctypes.c_int * nseg)(*Cs), ptrs(lab_dev),
+          int(labels[0].dtype == torch.int64), ptrs(val_dev), ptrs(dls) if dls is not None else None,
+          (ctypes.c_long * nseg)(*lddls), ptrs(tp), ptrs(fn), float(alpha), float(gamma), int(k), int(loss_kind),
+          _p(loss), _p(row_loss), _p(hit), _stream())
+    return (loss if loss_kind else None), (dls if want_grad else None), hit  # loss_kind 0 writes neither
 
 
 def check_finite(g, found_inf):
