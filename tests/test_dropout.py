@@ -27,7 +27,8 @@ def _mix(x):
 
 
 def drop_thresh(p):
-    t = p * 4294967296.0
+    """round(p * 2^32) of the f32 value of p: vj_dropout's p argument is a float (vj_drop_thresh)."""
+    t = float(np.float32(p)) * 4294967296.0
     return 0 if t <= 0 else (M32 if t >= M32 else int(t + 0.5))
 
 

@@ -1378,8 +1378,11 @@ extern "C" int vj_add_rows(int R, int D, float* dst, long ldd, const float* tabl
 extern "C" int vj_pred_index(int B, int K, int Kp, const long* mx, const long* my, int row0, int bmod, int N, int* pos,
                              int* ctx_dst, int* tgt_rows, int* loss_rows, void* stream) {
   if (B == 0) return VJ_OK;
+  VJ_CHECK_ARG(B > 0 && K >= 0 && K <= 16384 && Kp >= 0 && Kp <= 16384 && bmod >= 0 && row0 >= 0,
+               "vj_pred_index: size out of range (B %d, K %d, Kp %d, bmod %d, row0 %d)", B, K, Kp, bmod, row0);
   const int n = K + Kp;
   VJ_CHECK_ARG(n >= 1 && n <= 16384, "vj_pred_index: sequence length %d out of range", n);
+  VJ_CHECK_ARG(pos && (K == 0 || (mx && ctx_dst)) && (Kp == 0 || (my && tgt_rows)), "vj_pred_index: null argument");
   hipLaunchKernelGGL(k_pred_index, dim3(B), dim3(256), n * sizeof(int), (hipStream_t)stream, K, Kp, mx, my, row0,
                      bmod > 0 ? bmod : B, N, pos, ctx_dst, tgt_rows, loss_rows);
   VJ_LAUNCH_CHECK("vj_pred_index");
