@@ -342,6 +342,47 @@ int vj_focal(int B, int nseg, const float* const* logits, const long* ld, const 
              int* const* tp, int* const* fn, float alpha, float gamma, int k, int loss_kind, float* loss,
              float* row_loss, int* hit, void* stream);
 
+/* Goal-image planning with the action-conditioned predictor (vj_plan.hip): the stages of the reference's
+ * cross-entropy-method loop between two predictor forwards (notebooks/utils/mpc_utils.py cem /
+ * compute_new_pose, world_model_wrapper.py step_predictor). All operands f32 on the device, nothing is read
+ * back, float sums are fixed-order (bitwise reproducible).
+ *
+ * vj_cem_sample: every sampled action of one CEM iteration (mpc_utils.py:93-107). noise [rollout][S][4],
+ * mean / std [rollout][4] (16-byte aligned), actions [S][rollout][7]. Per (s, h): a = noise * std[h] + mean[h]
+ * (an f32 multiply, then an f32 add), a[0..2] clipped to +-maxnorm, a[3] to +-gripper_clip, then a[c] =
+ * axis_val[c] where axis_on[c] (HOST arrays of 4, read before the call returns; axis_on NULL = none),
+ * actions[s][h] = (a0, a1, a2, 0, 0, 0, a3), the last 1.0 where close_from >= 0 and h >= close_from. */
+int vj_cem_sample(int S, int rollout, const float* noise, const float* mean, const float* std, float maxnorm,
+                  float gripper_clip, const int* axis_on, const float* axis_val, int close_from, float* actions,
+                  void* stream);
+/* compute_new_pose (mpc_utils.py:166-190) for S rows of (x, y, z, roll, pitch, yaw, gripper), row strides >= 7:
+ * xyz = pose + action (f32), gripper = clip(pose + action, 0, 1) (f32), angles = euler_xyz(R(action[3:6])
+ * R(pose[3:6])) with scipy's lowercase "xyz" (extrinsic) convention, R(a, b, c) = Rz(c) Ry(b) Rx(a), computed in
+ * f64 and rounded once: roll and yaw in (-pi, pi], pitch in [-pi/2, pi/2]. At gimbal lock (cos(pitch) <= 1e-7)
+ * yaw = 0 and roll carries the remaining rotation. out may alias neither input. */
+int vj_pose_step(int S, const float* pose, long ldp, const float* action, long lda, float* out, long ldo,
+                 void* stream);
+/* One rollout step's newest frame: for each of S samples, R rows of width D at src + s * src_sample_stride +
+ * r * src_row_stride (the last frame of the predictor output, no slice copy). normalize != 0: y =
+ * F.layer_norm(x, (D,)) without affine (biased variance, eps; a zero-variance row gives zeros), else y = x.
+ * dst != NULL: y -> dst + s * dst_sample_stride + r * D (the next slot of the frame trajectory). energy !=
+ * NULL: energy[s] = mean over R * D of |y - goal|, goal [R][D] shared by every sample. D % 4 == 0, D <= 2048,
+ * strides multiples of 4 floats, pointers 16-byte aligned. */
+int vj_plan_frame(int S, int R, int D, const float* src, long src_sample_stride, long src_row_stride, int normalize,
+                  float eps, float* dst, long dst_sample_stride, const float* goal, float* energy, void* stream);
+/* Elite selection and the momentum update of one CEM iteration in one launch (one workgroup; mpc_utils.py:
+ * 120-150). energy [S], actions [S][rollout][7], mean / std [rollout][4] updated IN PLACE, elite_idx int32 [k]
+ * or NULL. The elites are the k smallest energies by rank count: rank(i) = #{j : e_j < e_i} + #{j < i : e_j ==
+ * e_i}, elite iff rank < k; ties go to the lower index, a NaN ranks after every number (NaNs among themselves
+ * by index). elite_idx lists them ascending by index. Over the elites, columns 0, 1, 2, 6: m = the f32 sum in
+ * rank order divided by k (the reference's own arithmetic on its gathered top-k rows), s = the unbiased
+ * standard deviation (two-pass, f64, rounded once: a constant column gives exactly 0), then
+ * mean = m * (1 - mm) + mean * mm and std = s * (1 - ms) + std * ms in f32, with (momentum_mean, momentum_std)
+ * for xyz and the gripper pair for column 6. 2 <= k <= S <= 4096. */
+int vj_cem_update(int S, int rollout, int k, const float* energy, const float* actions, double momentum_mean,
+                  double momentum_std, double momentum_mean_gripper, double momentum_std_gripper, float* mean,
+                  float* std, int* elite_idx, void* stream);
+
 /* fp32-operand parity mode (vj_f32.hip): the encoder forward with f32 operands throughout, to show
  * the bf16 path's distance from the fp32 reference is operand rounding only. Not on the training
  * path. vj_gemm_f32: C = A B^T + bias (+ resid), epi as vj_gemm_bf16 (F32 = 1, F32_RESID = 2,

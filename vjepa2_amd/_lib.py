@@ -18,6 +18,7 @@ _I = ctypes.c_int
 _L = ctypes.c_long
 _F = ctypes.c_float
 _U = ctypes.c_uint
+_D = ctypes.c_double
 
 # name -> argtypes (restype is always int)
 SIGNATURES = {
@@ -83,6 +84,10 @@ SIGNATURES = {
     "vj_xattn_bwd": [_I, _I, _I, _I, _I, _P, _L, _P, _L, _P, _L, _P, _L, _P, _F, _P, _L, _P, _L, _P, _L, _P],
     "vj_xent": [_I, _I, _I, _P, _L, _P, _I, _P, _P, _P, _L, _P, _P, _P],
     "vj_focal": [_I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _F, _F, _I, _I, _P, _P, _P, _P],
+    "vj_cem_sample": [_I, _I, _P, _P, _P, _F, _F, _P, _P, _I, _P, _P],
+    "vj_pose_step": [_I, _P, _L, _P, _L, _P, _L, _P],
+    "vj_plan_frame": [_I, _I, _I, _P, _L, _L, _I, _F, _P, _L, _P, _P, _P],
+    "vj_cem_update": [_I, _I, _I, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P],
 }
 
 _lib = None

@@ -821,6 +821,128 @@ def focal(logits, labels, tp, fn, valid=None, alpha=0.25, gamma=2.0, k=5, loss_k
     return (loss if loss_kind else None), (dls if want_grad else None), hit  # loss_kind 0 writes neither
 
 
+# ------------------------------------------------------------------------------------------------
+# Goal-image planning (vj_plan.hip; notebooks/utils/mpc_utils.py, world_model_wrapper.py)
+def _f32_contig(t, shape, name):
+    if t.dtype != F32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous f32 {tuple(shape)} tensor, got {t.dtype} {tuple(t.shape)} "
+                         f"{t.stride()}")
+
+
+def _rows7(t, name):
+    """[S, 7] f32 rows with unit column stride -> row stride."""
+    if t.dtype != F32 or t.dim() != 2 or t.shape[1] != 7 or t.stride(1) != 1:
+        raise ValueError(f"{name}: expected f32 [S, 7] rows (stride(1) == 1), got {t.dtype} {tuple(t.shape)} "
+                         f"{t.stride()}")
+    return t.stride(0)
+
+
+def cem_sample(noise, mean, std, maxnorm, axis=None, close_from=None, gripper_clip=0.75, out=None):
+    """Every sampled action of one CEM iteration (vj_cem_sample; mpc_utils.py:93-107).
+
+    noise f32 [rollout, S, 4], mean / std f32 [rollout, 4] (device). axis: {column 0..3: value} overrides (the
+    reference's ``axis`` dict), close_from: the reference's ``close_gripper`` (None: never). Returns actions f32
+    [S, rollout, 7] (``out`` if given)."""
+    _dev(noise, mean, std, out)
+    if noise.dim() != 3 or noise.shape[2] != 4:
+        raise ValueError(f"cem_sample: noise must be [rollout, S, 4], got {tuple(noise.shape)}")
+    rollout, S, _ = noise.shape
+    _f32_contig(noise, (rollout, S, 4), "cem_sample: noise")
+    _f32_contig(mean, (rollout, 4), "cem_sample: mean")
+    _f32_contig(std, (rollout, 4), "cem_sample: std")
+    if out is None:
+        out = torch.empty(S, rollout, 7, dtype=F32, device=noise.device)
+    _f32_contig(out, (S, rollout, 7), "cem_sample: out")
+    on, val = [0] * 4, [0.0] * 4
+    for ax, v in (axis or {}).items():
+        if ax not in (0, 1, 2, 3):
+            raise ValueError(f"cem_sample: axis key {ax!r} is not one of the sampled columns 0..3")
+        on[ax], val[ax] = 1, float(v)
+    close = -1 if close_from is None else int(close_from)
+    if close < -1:
+        raise ValueError(f"cem_sample: close_from {close_from} must be None or a rollout step >= 0")
+    _call("vj_cem_sample", S, rollout, _p(noise), _p(mean), _p(std), float(maxnorm), float(gripper_clip),
+          int_array(on), (ctypes.c_float * 4)(*val), close, _p(out), _stream())
+    return out
+
+
+def pose_step(pose, action, out=None):
+    """compute_new_pose (vj_pose_step; mpc_utils.py:166-190) on device rows: pose, action f32 [S, 7] (row
+    stride >= 7) -> new pose f32 [S, 7] (``out`` if given, which may be a strided view too)."""
+    _dev(pose, action, out)
+    ldp, lda = _rows7(pose, "pose_step: pose"), _rows7(action, "pose_step: action")
+    S = pose.shape[0]
+    if action.shape[0] != S:
+        raise ValueError(f"pose_step: {S} poses but {action.shape[0]} actions")
+    if out is None:
+        out = torch.empty(S, 7, dtype=F32, device=pose.device)
+    ldo = _rows7(out, "pose_step: out")
+    if out.shape[0] != S:
+        raise ValueError(f"pose_step: out has {out.shape[0]} rows for {S} poses")
+    _call("vj_pose_step", S, _p(pose), ldp, _p(action), lda, _p(out), ldo, _stream())
+    return out
+
+
+def plan_frame(src, goal=None, dst=None, normalize=True, energy=None, want_energy=None, eps=1e-5):
+    """Newest predicted frame of S samples -> normalised copy in the trajectory and / or L1 energy to the goal
+    (vj_plan_frame; world_model_wrapper.py:59-62, mpc_utils.py:17-18, 122).
+
+    src f32 [S, R, D] view with stride(2) == 1 (e.g. ``pred_out.view(S, T, hw, D)[:, -1]``: no copy is made),
+    goal f32 [R, D] contiguous, dst f32 [S, R, D] view with contiguous samples (stride(1) == D, stride(2) == 1),
+    energy f32 [S]. want_energy defaults to ``goal is not None``. Returns (dst, energy), either may be None."""
+    _dev(src, goal, dst, energy)
+    if src.dtype != F32 or src.dim() != 3 or src.stride(2) != 1:
+        raise ValueError(f"plan_frame: src must be an f32 [S, R, D] view with stride(2) == 1, got {src.dtype} "
+                         f"{tuple(src.shape)} {src.stride()}")
+    S, R, D = src.shape
+    want_energy = (goal is not None) if want_energy is None else bool(want_energy)
+    if want_energy:
+        if goal is None:
+            raise ValueError("plan_frame: the energy needs a goal")
+        _f32_contig(goal, (R, D), "plan_frame: goal")
+        if energy is None:
+            energy = torch.empty(S, dtype=F32, device=src.device)
+        _f32_contig(energy, (S,), "plan_frame: energy")
+    else:
+        energy = None
+    lds = 0
+    if dst is not None:
+        if dst.dtype != F32 or tuple(dst.shape) != (S, R, D) or dst.stride(2) != 1 or dst.stride(1) != D:
+            raise ValueError(f"plan_frame: dst must be an f32 {(S, R, D)} view with contiguous samples, got "
+                             f"{dst.dtype} {tuple(dst.shape)} {dst.stride()}")
+        lds = dst.stride(0) if S > 1 else R * D
+    sr = src.stride(1) if R > 1 else D  # a size-1 dimension's stride is arbitrary
+    ss = src.stride(0) if S > 1 else (R - 1) * sr + D
+    _call("vj_plan_frame", S, R, D, _p(src), ss, sr, int(bool(normalize)), float(eps), _p(dst), lds,
+          _p(goal) if want_energy else None, _p(energy), _stream())
+    return dst, energy
+
+
+def cem_update(energy, actions, k, mean, std, momentum_mean=0.25, momentum_std=0.95, momentum_mean_gripper=0.15,
+               momentum_std_gripper=0.15, elite_idx=None, want_idx=False):
+    """Elite selection + momentum update of one CEM iteration in one launch (vj_cem_update; mpc_utils.py:
+    120-150). energy f32 [S], actions f32 [S, rollout, 7], mean / std f32 [rollout, 4] updated IN PLACE. The
+    elites are the k smallest energies (ties: lower index first; a NaN ranks last). Returns elite_idx (int32 [k],
+    ascending by index) if ``elite_idx`` is given or want_idx, else None."""
+    _dev(energy, actions, mean, std, elite_idx)
+    if actions.dim() != 3 or actions.shape[2] != 7:
+        raise ValueError(f"cem_update: actions must be [S, rollout, 7], got {tuple(actions.shape)}")
+    S, rollout, _ = actions.shape
+    _f32_contig(actions, (S, rollout, 7), "cem_update: actions")
+    _f32_contig(energy, (S,), "cem_update: energy")
+    _f32_contig(mean, (rollout, 4), "cem_update: mean")
+    _f32_contig(std, (rollout, 4), "cem_update: std")
+    k = int(k)
+    if elite_idx is None and want_idx:
+        elite_idx = torch.empty(max(k, 0), dtype=torch.int32, device=energy.device)
+    if elite_idx is not None and (elite_idx.dtype != torch.int32 or elite_idx.numel() < k
+                                  or not elite_idx.is_contiguous()):
+        raise ValueError(f"cem_update: elite_idx must be a contiguous int32 tensor of at least {k} entries")
+    _call("vj_cem_update", S, rollout, k, _p(energy), _p(actions), float(momentum_mean), float(momentum_std),
+          float(momentum_mean_gripper), float(momentum_std_gripper), _p(mean), _p(std), _p(elite_idx), _stream())
+    return elite_idx
+
+
 def check_finite(g, found_inf):
     _dev(g, found_inf)
     _call("vj_check_finite", g.numel(), _p(g), _p(found_inf), _stream())
