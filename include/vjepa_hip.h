@@ -109,6 +109,27 @@ int vj_attn_bwd_ex(int T, int H, int hd, const void* qkv, long ld, int q_off, in
                    long ldo, const void* dout, long lddo, float* stats, void* dqkv, long ldd, float scale, int ngroups,
                    const int* nseq, const int* len, const int* rope_ids, int rope_mod, int rope_tpf, int rope_tpr,
                    const float* cos_t, const float* sin_t, int fblk, float dropout_p, unsigned seed, void* stream);
+/* Forward attention of new queries over a K/V cache (inference: no dropout, no backward): the frame-causal
+ * F.scaled_dot_product_attention of ACRoPEAttention.forward (src/models/utils/modules.py:243-247, mask of
+ * modules.py:12-23) for the rows a rollout step appends, the earlier frames' keys and values being the ones an
+ * earlier call left in the cache (the reference recomputes them: notebooks/utils/world_model_wrapper.py:56-59).
+ * Queries: bf16 rows [nseq * qlen, ldq], head h at column q_off + h*hd, RoPE applied; query i of a sequence
+ * stands at position q_pos0 + i. Keys / values: sequence s at kv + s * kv_seq_stride (elements), rows of ldkv,
+ * K at column k_off + h*hd, V at v_off + h*hd; the first klen rows are valid. Rows at and past klen are never
+ * read as data (they may hold anything, NaN included). fblk > 0: query i sees key j iff j / fblk <=
+ * (q_pos0 + i) / fblk; fblk = 0: every key below klen. q_pos0 + qlen <= klen; nseq > 1: klen <=
+ * kv_seq_stride / ldkv. O bf16 [nseq * qlen, ldo] at column h*hd. stats: NULL, or f32 [H][nseq * qlen], the
+ * log2-sum-exp2 as vj_attn_fwd's stats[0]. Strides and offsets multiples of 8, pointers 16-byte aligned, a
+ * sequence's keys below 2 GB. head_dim 32 or 64; 80 and 88 return VJ_ERR_UNSUPPORTED (3). */
+int vj_attn_fwd_kv(int nseq, int qlen, int klen, int H, int hd, const void* q, long ldq, int q_off, const void* kv,
+                   long kv_seq_stride, long ldkv, int k_off, int v_off, void* o, long ldo, float* stats, float scale,
+                   int q_pos0, int fblk, void* stream);
+/* Appends to that cache: rows [row0, row0 + nrows) of every sequence's slot, columns [dst_off, dst_off + width)
+ * := columns [src_off, src_off + width) of the nseq * nrows bf16 rows of src (row stride lds): the K | V
+ * columns of the new rows' QKV projection (modules.py:330). Bit-exact; no other element of the cache is
+ * written. width, strides and offsets multiples of 8, pointers 16-byte aligned. */
+int vj_kv_append(int nseq, int nrows, int width, const void* src, long lds, int src_off, void* kv, long kv_seq_stride,
+                 long ldkv, int dst_off, int row0, void* stream);
 
 /* Fused QKV projection + RoPE of q and k: C[M, 3*H*hd] (bf16) = A[M,K] W[3*H*hd, K]^T + bias, then
  * q, k columns rotated (modules.py:330 + 343-365) in the GEMM epilogue. Same RoPE arguments as vj_rope;

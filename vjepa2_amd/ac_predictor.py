@@ -42,6 +42,56 @@ class _ScatterRowsFn(torch.autograd.Function):
         return (None, None) + tuple(ops.gather_rows(dseq, idx) for idx in ctx.idxs)
 
 
+class ACRolloutCache:
+    """Per-block keys and values of the frames a rollout has fed so far (VisionTransformerPredictorAC.new_cache /
+    forward_cached). The predictor's attention is frame-causal: the hidden states of frames 0 .. t-1, and so
+    their keys and values in every block, do not depend on frame t, and a rollout that appends one frame per
+    step needs only the new frame's rows through the GEMMs.
+
+    kv[i]: block i's bf16 [batch, max_frames * n_t, 2 * H * hd] buffer (K | V columns, RoPE applied to K),
+    n_t = cond + H*W tokens per frame, sample-major so a sequence's keys are contiguous. Allocated once:
+    depth * batch * max_frames * n_t * 2 * D * 2 bytes (DROID planning, 400 samples, 2 frames, n_t 258,
+    D 1024, 24 blocks: 400 * 2 * 258 * 4096 B * 24 = 20.3 GB). `frames` is a host counter: the rows of frames
+    >= `frames` are stale and never read (vj_attn_fwd_kv sees the first frames * n_t rows only), so rewind()
+    and reset() do no device work."""
+
+    def __init__(self, depth, batch, max_frames, n_t, width, hw, grid_w, cond, device):
+        self.batch, self.max_frames, self.n_t, self.cond = int(batch), int(max_frames), int(n_t), int(cond)
+        self.hw, self.grid_w = int(hw), int(grid_w)
+        self.frames = 0
+        self.kv = [torch.empty(self.batch, self.max_frames * self.n_t, 2 * width, dtype=torch.bfloat16, device=device)
+                   for _ in range(depth)]
+        self._layouts = {}
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self.kv)
+
+    def rewind(self, t):
+        """Forget the frames from t on (0 <= t <= frames): the next forward_cached appends at frame t."""
+        t = int(t)
+        if not 0 <= t <= self.frames:
+            raise ValueError(f"rewind({t}): the cache holds {self.frames} frames")
+        self.frames = t
+
+    def reset(self):
+        self.rewind(0)
+
+    def layout(self, t0, tn):
+        """ac_token_layout's TokenLayout for the rows of frames t0 .. t0 + tn - 1 alone: the same RoPE ids those
+        rows have in the full sequence, ids_mod (and so the RoPE tables) sized for max_frames whatever t0."""
+        lay = self._layouts.get((t0, tn))
+        if lay is None:
+            dev = self.kv[0].device
+            t = torch.arange(t0, t0 + tn, device=dev)[:, None]
+            j = torch.arange(self.n_t, device=dev)[None, :]
+            ids = torch.where(j < self.cond, t * self.hw, t * self.hw + (j - self.cond))
+            ids = ids.reshape(1, -1).expand(self.batch, -1).reshape(-1).to(torch.int32).contiguous()
+            lay = fn.TokenLayout([(self.batch, tn * self.n_t)], ids=ids, ids_mod=self.max_frames * self.hw,
+                                 tpf=self.hw, tpr=self.grid_w, fblk=self.n_t)
+            self._layouts[(t0, tn)] = lay
+        return lay
+
+
 class VisionTransformerPredictorAC(nn.Module):
     """ac_predictor.py:17-190."""
 
@@ -146,6 +196,83 @@ class VisionTransformerPredictorAC(nn.Module):
         y = fn.run_layernorm(rows, self.predictor_norm, out_dtype=torch.bfloat16)
         out = fn.run_linear(y, self.predictor_proj, out_dtype=torch.float32)
         return out.reshape(B, T * hw, -1)
+
+    def new_cache(self, batch, max_frames):
+        """An ACRolloutCache for forward_cached: `batch` sequences of up to `max_frames` frames. One bf16
+        [batch, max_frames * n_t, 2 * predictor_embed_dim] buffer per block (sizes: ACRolloutCache)."""
+        if not self.is_frame_causal:
+            raise ValueError("new_cache: the predictor is not frame-causal (is_frame_causal=False): earlier frames "
+                             "see later ones, so their keys and values cannot be cached")
+        if max_frames < 1 or batch < 1:
+            raise ValueError(f"new_cache: batch {batch} and max_frames {max_frames} must be >= 1")
+        if max_frames > self.num_frames // self.tubelet_size:
+            raise ValueError(f"new_cache: max_frames {max_frames} exceeds the {self.num_frames // self.tubelet_size} "
+                             "frames the frame-causal mask was built for (num_frames // tubelet_size)")
+        cond = 3 if self.use_extrinsics else 2
+        hw = self.grid_height * self.grid_width
+        width = self.predictor_embed.weight.shape[0]
+        return ACRolloutCache(len(self.predictor_blocks), batch, max_frames, cond + hw, width, hw, self.grid_width,
+                              cond, self.predictor_embed.weight.device)
+
+    def forward_cached(self, x_new, actions_new, states_new, extrinsics_new=None, *, cache):
+        """forward() one chunk of frames at a time: x_new [B, Tn*H*W, embed_dim], actions_new / states_new
+        [B, Tn, 7] (extrinsics_new [B, Tn, 6]) are frames t0 .. t0 + Tn - 1 of a sequence whose first
+        t0 = cache.frames frames earlier calls fed. Returns [B, Tn*H*W, embed_dim] (f32), mathematically rows
+        [t0*H*W, (t0 + Tn)*H*W) of forward() over all t0 + Tn frames, and advances cache.frames by Tn. Only the
+        new rows go through the GEMMs; their attention reads the earlier frames' keys and values from the
+        cache. Inference only, frame-causal predictors only, no active dropout / drop_path."""
+        hw = self.grid_height * self.grid_width
+        B, N_new, C = x_new.shape
+        Tn = N_new // hw
+        cond = 3 if self.use_extrinsics else 2
+        # every refusal before any device work, the cache untouched
+        if not isinstance(cache, ACRolloutCache):
+            raise TypeError("forward_cached: cache must be an ACRolloutCache (predictor.new_cache)")
+        if not self.is_frame_causal:
+            raise ValueError("forward_cached: the predictor is not frame-causal (is_frame_causal=False): the cached "
+                             "keys and values of earlier frames would be invalid")
+        if torch.is_grad_enabled():
+            ins = [t for t in (x_new, actions_new, states_new, extrinsics_new) if t is not None]
+            if any(t.requires_grad for t in ins) or any(p.requires_grad for p in self.parameters()):
+                raise RuntimeError("forward_cached is inference only (there is no backward through the cache): call it "
+                                   "under torch.no_grad(), or with no input or parameter requiring grad")
+        for i, blk in enumerate(self.predictor_blocks):
+            why = fn.cached_block_refusal(blk)
+            if why is not None:
+                raise RuntimeError(f"forward_cached: block {i}: {why}; the cached forward is the deterministic "
+                                   "inference path (call eval(), drop rates 0)")
+        if Tn < 1 or N_new != Tn * hw:
+            raise ValueError(f"forward_cached: {N_new} tokens are not whole frames of {hw}")
+        if B != cache.batch:
+            raise ValueError(f"forward_cached: batch {B} != cache.batch {cache.batch}")
+        if (cache.n_t, cache.cond, len(cache.kv)) != (cond + hw, cond, len(self.predictor_blocks)):
+            raise ValueError("forward_cached: the cache was made for another predictor")
+        t0 = cache.frames
+        if t0 + Tn > cache.max_frames:
+            raise ValueError(f"forward_cached: {t0} cached + {Tn} new frames exceed the cache's max_frames "
+                             f"{cache.max_frames}")
+        if actions_new.shape[:2] != (B, Tn) or states_new.shape[:2] != (B, Tn):
+            raise ValueError(f"forward_cached: actions / states must be [{B}, {Tn}, 7]")
+        if self.use_extrinsics and extrinsics_new is None:
+            raise ValueError("forward_cached: the predictor uses extrinsics")
+        n_t = cond + hw
+        e = fn.run_linear(x_new.reshape(B * N_new, C), self.predictor_embed, out_dtype=torch.float32)
+        a = fn.run_linear(actions_new.reshape(B * Tn, -1), self.action_encoder, out_dtype=torch.float32)
+        s = fn.run_linear(states_new.reshape(B * Tn, -1), self.state_encoder, out_dtype=torch.float32)
+        srcs = [a, s]
+        if self.use_extrinsics:
+            srcs.append(fn.run_linear(extrinsics_new.reshape(B * Tn, -1), self.extrinsics_encoder,
+                                      out_dtype=torch.float32))
+        conds, frame = self._indices(B, Tn, cond, x_new.device)
+        seq = _ScatterRowsFn.apply(B * Tn * n_t, conds + [frame], *srcs, e)
+        lay = cache.layout(t0, Tn)
+        for blk, kv in zip(self.predictor_blocks, cache.kv):
+            seq = fn.block_forward_cached(seq, blk, lay, kv, t0 * n_t)
+        rows = fn.gather_rows(seq, frame)
+        y = fn.run_layernorm(rows, self.predictor_norm, out_dtype=torch.bfloat16)
+        out = fn.run_linear(y, self.predictor_proj, out_dtype=torch.float32)
+        cache.frames = t0 + Tn
+        return out.reshape(B, Tn * hw, -1)
 
 
 def vit_ac_predictor(**kwargs):

@@ -972,6 +972,236 @@ __global__ __launch_bounds__(256, (HD == 64 ? DQ64_OCC : 1)) void k_attn_bwd_dq(
   }
 }
 
+// ------------------------------------------------------------------------------------------------
+// Forward over a K/V cache with a query position offset (vj_attn_fwd_kv): k_attn_fwd's sweep (128-query
+// workgroups, 32 queries per wave, 64-key tiles double-buffered, deferred-max softmax) with the queries
+// and the keys in buffers of their own. No dropout; stats optional. A kernel of its own: with the sweep
+// moved into one __forceinline__ function called by both kernels, k_attn_fwd<64> compiled to 162 VGPRs
+// instead of 160 (its dropout form 200 for 198, head dims 80 / 88 202 for 201), so the training forward's
+// source stays as measured and this one repeats it ("Planning: KV cache").
+struct AttnKvArgs {
+  const bf16_t* q;  // [nseq * qlen, ldq], head h at column q_off + h * hd (RoPE applied)
+  long ldq;
+  int q_off;
+  const bf16_t* kv;  // sequence s at kv + s * kv_seq_stride, rows of ldkv, the first klen rows valid
+  long kv_seq_stride, ldkv;
+  int k_off, v_off;
+  bf16_t* o;  // [nseq * qlen, ldo]
+  long ldo;
+  float* stats;  // [H][nseq * qlen] lse2, or NULL
+  int H, nseq, qlen, klen;
+  int q_pos0;  // position of the call's first query in its sequence
+  int fblk;    // > 0: query i sees key j iff j / fblk <= (q_pos0 + i) / fblk; 0: every key below klen
+  float scale;
+};
+
+template <int HD>
+__global__ __launch_bounds__(256, FWD_OCC) void k_attn_fwd_kv(AttnKvArgs a) {
+  static_assert(HD == Hd<HD>::P, "head dims without LDS padding only (stage_rows' range-checked path)");
+  constexpr int HDP = HD;
+  constexpr int KT = 64;
+  constexpr int TB = KT * HDP * 2;  // bytes per K or V tile
+  __shared__ __attribute__((aligned(16))) char smem_raw[4 * TB];
+  LDS_AS char* smem = (LDS_AS char*)smem_raw;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int tile_id, h;
+  xcd_tile(tile_id, h);
+  const int tps = (a.qlen + 127) / 128;
+  const int seq = tile_id / tps, qt = tile_id - seq * tps;
+  const int qlen = a.qlen, klen = a.klen;
+  const int qloc = qt * 128 + wave * 32 + (lane & 31);
+  const bool qok = qloc < qlen;
+  const int hl = lane >> 5;
+  const long qrow0 = (long)seq * qlen;
+  // this lane's key limit (fc_klim at the query's position in the sequence); the block's keys end at its
+  // last query's limit, and tiles past its first query's limit take the per-lane mask. Every limit is
+  // <= klen: rows of the cache from klen on are never visible.
+  const int klim = fc_klim(a.fblk, a.q_pos0 + qloc, klen);
+  const int kend = fc_klim(a.fblk, a.q_pos0 + min(qt * 128 + 127, qlen - 1), klen);
+  const int kmask0 = fc_klim(a.fblk, a.q_pos0 + qt * 128, klen);
+
+  bf16x8 qf[HDP / 16];
+  const bf16_t* qrow = a.q + (qrow0 + qloc) * a.ldq + a.q_off + h * HD;
+#pragma unroll
+  for (int s = 0; s < HDP / 16; ++s) qf[s] = gload8(qrow + 16 * s + 8 * hl, qok);
+
+  // The descriptors span exactly the klen valid rows of this sequence: a row at or past klen (stale data
+  // of an earlier call, whatever its bits) is out of range and zero-fills, so 0 * NaN never forms in PV.
+  const bf16_t* kbase = a.kv + (long)seq * a.kv_seq_stride + a.k_off + h * HD;
+  const bf16_t* vbase = a.kv + (long)seq * a.kv_seq_stride + a.v_off + h * HD;
+  const uint32_t bytes = (uint32_t)((long)klen * a.ldkv * 2);  // < 2^31, checked at launch
+  const __amdgpu_buffer_rsrc_t rk = make_rsrc(kbase, bytes);
+  const __amdgpu_buffer_rsrc_t rv = make_rsrc(vbase, bytes);
+
+  f32x16 ot[HDP / 32];
+  float lsum = 0.f;
+#pragma unroll
+  for (int r = 0; r < 16; ++r)
+#pragma unroll
+    for (int d = 0; d < HDP / 32; ++d) ot[d][r] = 0.f;
+  float m_use = -INFINITY, cm = 0.f;
+  const float c = a.scale * LOG2E;
+
+  uint32_t vlo[HDP / 32], vhi[HDP / 32];
+#pragma unroll
+  for (int d = 0; d < HDP / 32; ++d) {
+    vlo[d] = (uint32_t)(uintptr_t)smem + tr_lane_off<HDP>(d, 0, lane);
+    vhi[d] = (uint32_t)(uintptr_t)smem + tr_lane_off<HDP>(d, 1, lane);
+  }
+  const int nkt = (kend + KT - 1) / KT;
+  stage_rows<HD, KT>(rk, a.ldkv, 0, klen, smem, wave, lane, 4);
+  stage_rows<HD, KT>(rv, a.ldkv, 0, klen, smem + TB, wave, lane, 4);
+  __syncthreads();
+  constexpr bool PRIO = HD == 64;  // as k_attn_fwd
+  auto s_tile = [&](const LDS_AS char* Ks, f32x16 (&st)[2]) {
+    bf16x8 kf[2][HDP / 16];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int s = 0; s < HDP / 16; ++s) kf[kk][s] = row_frag<HDP>(Ks, kk * 32, s, lane);
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[kk][r] = 0.f;
+    if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+    for (int s = 0; s < HDP / 16; ++s)
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+        st[kk] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[kk][s], qf[s], st[kk], 0, 0, 0);
+    if (PRIO) __builtin_amdgcn_s_setprio(0);
+  };
+  // keys past the limit get -inf (the ragged last tile, frame boundaries inside the query range)
+  auto mask_tile = [&](const int kb, f32x16 (&st)[2]) {
+    if (kb + KT > kmask0) {
+      asm volatile("");
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          if (kb + kk * 32 + acc_row(r, lane) >= klim) st[kk][r] = -INFINITY;
+    }
+  };
+  auto to_row_max = [&](const f32x16 (&st)[2]) {
+    float mx = st[0][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) mx = fmaxf(mx, st[0][r]);
+#pragma unroll
+    for (int r = 0; r < 16; ++r) mx = fmaxf(mx, st[1][r]);
+    mx = max_xor32(mx);
+    const float m_new = fmaxf(m_use, mx);
+    const float alpha = __builtin_amdgcn_exp2f((m_use - m_new) * c);
+    m_use = m_new;
+    cm = m_new * c;
+#pragma unroll
+    for (int r = 0; r < 16; ++r)
+#pragma unroll
+      for (int d = 0; d < HDP / 32; ++d) ot[d][r] *= alpha;
+    lsum *= alpha;
+  };
+  auto exp_tile = [&](f32x16 (&st)[2]) {
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int r = 0; r < 16; ++r) st[kk][r] = __builtin_amdgcn_exp2f(fmaf(st[kk][r], c, -cm));
+    float ls0 = st[0][0], ls1 = st[1][0];
+#pragma unroll
+    for (int r = 1; r < 16; ++r) {
+      ls0 += st[0][r];
+      ls1 += st[1][r];
+    }
+    return ls0 + ls1;
+  };
+  constexpr float PLIM = 4096.f;  // deferred max: see k_attn_fwd
+  auto tile_iter = [&](const int kt, auto cur_c, auto first_c) {
+    constexpr int cur = decltype(cur_c)::value;
+    constexpr bool FIRST = decltype(first_c)::value;
+    const LDS_AS char* Ks = smem + cur * 2 * TB;
+    if (kt + 1 < nkt) {
+      LDS_AS char* nx = smem + (cur ^ 1) * 2 * TB;
+      stage_rows<HD, KT>(rk, a.ldkv, (kt + 1) * KT, klen, nx, wave, lane, 4);
+      stage_rows<HD, KT>(rv, a.ldkv, (kt + 1) * KT, klen, nx + TB, wave, lane, 4);
+    }
+    f32x16 st[2];
+    s_tile(Ks, st);
+    constexpr int VIMG = cur * 2 * TB + TB;
+    bf16x8 vf[4][HDP / 32];
+#pragma unroll
+    for (int d = 0; d < HDP / 32; ++d) {
+      vf[0][d] = tr_frag_at<HDP, VIMG, 0>(vlo[d], vhi[d]);
+      vf[1][d] = tr_frag_at<HDP, VIMG, 16>(vlo[d], vhi[d]);
+      vf[2][d] = tr_frag_at<HDP, VIMG, 32>(vlo[d], vhi[d]);
+      vf[3][d] = tr_frag_at<HDP, VIMG, 48>(vlo[d], vhi[d]);
+    }
+    const int kb = kt * KT;
+    mask_tile(kb, st);
+    if constexpr (FIRST) to_row_max(st);
+    float ls = exp_tile(st);
+    if constexpr (!FIRST) {
+      if (__builtin_amdgcn_ballot_w64(!(ls <= PLIM))) {
+        asm volatile("");
+        lds_wait();
+        s_tile(Ks, st);
+        mask_tile(kb, st);
+        to_row_max(st);
+        ls = exp_tile(st);
+      }
+    }
+    lsum += ls;
+    lds_wait();
+    {
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) tie(vf[ks]);
+      if (PRIO) __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int ks = 0; ks < 4; ++ks) {
+        const bf16x8 pf = acc_frag(st[ks >> 1], ks & 1);
+#pragma unroll
+        for (int d = 0; d < HDP / 32; ++d) ot[d] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[ks][d], pf, ot[d], 0, 0, 0);
+      }
+      if (PRIO) __builtin_amdgcn_s_setprio(0);
+    }
+    __syncthreads();
+  };
+  using I0 = std::integral_constant<int, 0>;
+  using I1 = std::integral_constant<int, 1>;
+  tile_iter(0, I0{}, std::true_type{});
+  for (int kt0 = 1; kt0 < nkt; kt0 += 2) {
+    tile_iter(kt0, I1{}, std::false_type{});
+    if (kt0 + 1 < nkt) tile_iter(kt0 + 1, I0{}, std::false_type{});
+  }
+  const float l_tot = sum_xor32(lsum);
+  const float inv = 1.f / l_tot;
+  if constexpr (HD == 32) {
+    if (qok) {
+      bf16_t* orow = a.o + (qrow0 + qloc) * a.ldo + h * HD;
+#pragma unroll
+      for (int r = 0; r < 16; r += 2) *(uint32_t*)(orow + acc_row(r, lane)) = pack_bf2(ot[0][r] * inv, ot[0][r + 1] * inv);
+    }
+  } else {
+    static_assert(4 * OutTile<HD>::BYTES <= 4 * TB, "output images fit the K / V buffers");
+    const int q0 = qt * 128 + wave * 32;
+    wave_store_rows<HD>(ot, inv, smem + wave * OutTile<HD>::BYTES, a.o + (qrow0 + q0) * a.ldo + h * HD, a.ldo,
+                        qlen - q0, lane);
+  }
+  if (a.stats && qok && hl == 0) a.stats[(long)h * a.nseq * qlen + qrow0 + qloc] = m_use * c + __log2f(l_tot);
+}
+
+// K | V columns of the new rows of a QKV GEMM output into their slots of the cache: 16-B pieces, one row per
+// group of `chunks` lanes. Rows of the cache outside [row0, row0 + nrows) of each sequence are not touched.
+__global__ __launch_bounds__(256) void k_kv_append(const bf16_t* src, long lds_, int src_off, bf16_t* kv,
+                                                   long kv_seq_stride, long ldkv, int dst_off, int row0, int nrows,
+                                                   int chunks, long total) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= total) return;
+  const long row = i / chunks;
+  const int c = (int)(i - row * chunks);
+  const long seq = row / nrows;
+  const int r = (int)(row - seq * nrows);
+  const i32x4 v = *(const i32x4*)(src + row * lds_ + src_off + c * 8);
+  *(i32x4*)(kv + seq * kv_seq_stride + (long)(row0 + r) * ldkv + dst_off + c * 8) = v;
+}
+
 int fill_groups(SeqGroups& sg, int ngroups, const int* nseq, const int* len, int tile, long T) {
   VJ_CHECK_ARG(ngroups >= 1 && ngroups <= MAXG, "attention: 1..%d sequence groups supported (got %d)", MAXG, ngroups);
   sg.ngroups = ngroups;
@@ -1139,4 +1369,84 @@ extern "C" int vj_attn_bwd(int T, int H, int hd, const void* qkv, long ld, int q
                            void* stream) {
   return vj_attn_bwd_ex(T, H, hd, qkv, ld, q_off, k_off, v_off, o, ldo, dout, lddo, stats, dqkv, ldd, scale, ngroups,
                         nseq, len, rope_ids, rope_mod, rope_tpf, rope_tpr, cos_t, sin_t, 0, 0.f, 0u, stream);
+}
+
+// Forward over a K/V cache the kernel does not own, queries at positions q_pos0 .. q_pos0 + qlen - 1 of their
+// sequences (include/vjepa_hip.h). Inference only: no dropout, stats optional. Every argument is checked
+// before any device work.
+extern "C" int vj_attn_fwd_kv(int nseq, int qlen, int klen, int H, int hd, const void* q, long ldq, int q_off,
+                              const void* kv, long kv_seq_stride, long ldkv, int k_off, int v_off, void* o, long ldo,
+                              float* stats, float scale, int q_pos0, int fblk, void* stream) {
+  VJ_CHECK_ARG(q && kv && o, "vj_attn_fwd_kv: null operand (q %p, kv %p, o %p)", q, kv, o);
+  VJ_CHECK_ARG(nseq >= 1 && qlen >= 1 && klen >= 1, "vj_attn_fwd_kv: nseq, qlen and klen must be >= 1 (got %d, %d, %d)",
+               nseq, qlen, klen);
+  VJ_CHECK_ARG(hd == 32 || hd == 64 || hd == 80 || hd == 88,
+               "vj_attn_fwd_kv: head_dim must be 32, 64, 80 or 88 (got %d)", hd);
+  if (hd != 32 && hd != 64) {
+    vj_set_error("vj_attn_fwd_kv: head_dim %d is not built for the cached forward (32 and 64 are)", hd);
+    return VJ_ERR_UNSUPPORTED;
+  }
+  VJ_CHECK_ARG(H >= 1 && H <= 65535, "vj_attn_fwd_kv: bad H=%d", H);
+  VJ_CHECK_ARG(fblk >= 0, "vj_attn_fwd_kv: bad frame block %d", fblk);
+  VJ_CHECK_ARG(q_pos0 >= 0 && (long)q_pos0 + qlen <= klen,
+               "vj_attn_fwd_kv: queries at positions %d .. %ld reach past the %d valid keys (q_pos0 + qlen > klen)",
+               q_pos0, (long)q_pos0 + qlen - 1, klen);
+  VJ_CHECK_ARG(ldq % 8 == 0 && ldkv % 8 == 0 && ldo % 8 == 0 && kv_seq_stride % 8 == 0,
+               "vj_attn_fwd_kv: row and sequence strides must be multiples of 8 (ldq %ld, ldkv %ld, ldo %ld, "
+               "kv_seq_stride %ld)", ldq, ldkv, ldo, kv_seq_stride);
+  VJ_CHECK_ARG(q_off >= 0 && k_off >= 0 && v_off >= 0 && q_off % 8 == 0 && k_off % 8 == 0 && v_off % 8 == 0,
+               "vj_attn_fwd_kv: q / k / v column offsets must be non-negative multiples of 8 (got %d, %d, %d)", q_off,
+               k_off, v_off);
+  const long D = (long)H * hd;
+  VJ_CHECK_ARG(ldq >= q_off + D && ldo >= D && ldkv >= k_off + D && ldkv >= v_off + D,
+               "vj_attn_fwd_kv: a row stride is shorter than its columns (ldq %ld, ldkv %ld, ldo %ld, H * hd %ld)",
+               ldq, ldkv, ldo, D);
+  VJ_CHECK_ARG(nseq == 1 || (kv_seq_stride >= ldkv && klen <= kv_seq_stride / ldkv),
+               "vj_attn_fwd_kv: klen %d exceeds the %ld rows of a sequence's cache slot (kv_seq_stride / ldkv)", klen,
+               ldkv ? kv_seq_stride / ldkv : 0L);
+  VJ_CHECK_ARG(((long)klen + 128) * ldkv * 2 <= 0x7fffffffL,
+               "vj_attn_fwd_kv: a sequence's keys span %ld bytes, past the 2 GB of a buffer descriptor",
+               (long)klen * ldkv * 2);
+  VJ_CHECK_ARG(((uintptr_t)q | (uintptr_t)kv | (uintptr_t)o) % 16 == 0 && (uintptr_t)stats % 4 == 0,
+               "vj_attn_fwd_kv: q, kv and o must be 16-byte aligned");
+  const long tiles = (long)nseq * ((qlen + 127) / 128);
+  VJ_CHECK_ARG(tiles <= 0x7fffffffL && (long)nseq * qlen <= 0x7fffffffL, "vj_attn_fwd_kv: too many query rows");
+  AttnKvArgs a{};
+  a.q = (const bf16_t*)q; a.ldq = ldq; a.q_off = q_off;
+  a.kv = (const bf16_t*)kv; a.kv_seq_stride = kv_seq_stride; a.ldkv = ldkv; a.k_off = k_off; a.v_off = v_off;
+  a.o = (bf16_t*)o; a.ldo = ldo; a.stats = stats;
+  a.H = H; a.nseq = nseq; a.qlen = qlen; a.klen = klen; a.q_pos0 = q_pos0; a.fblk = fblk; a.scale = scale;
+  const dim3 grid((unsigned)tiles, H);
+  hipStream_t st = (hipStream_t)stream;
+  if (hd == 64) hipLaunchKernelGGL((k_attn_fwd_kv<64>), grid, dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((k_attn_fwd_kv<32>), grid, dim3(256), 0, st, a);
+  VJ_LAUNCH_CHECK("vj_attn_fwd_kv");
+  return VJ_OK;
+}
+
+// Rows [row0, row0 + nrows) of every sequence's cache slot := columns [src_off, src_off + width) of the
+// nseq * nrows rows of src (the K | V columns of the new rows' QKV projection). Bit-exact copy.
+extern "C" int vj_kv_append(int nseq, int nrows, int width, const void* src, long lds, int src_off, void* kv,
+                            long kv_seq_stride, long ldkv, int dst_off, int row0, void* stream) {
+  VJ_CHECK_ARG(src && kv, "vj_kv_append: null operand (src %p, kv %p)", src, kv);
+  VJ_CHECK_ARG(nseq >= 1 && nrows >= 1 && width >= 8, "vj_kv_append: nseq, nrows >= 1 and width >= 8 (got %d, %d, %d)",
+               nseq, nrows, width);
+  VJ_CHECK_ARG(row0 >= 0, "vj_kv_append: bad first row %d", row0);
+  VJ_CHECK_ARG(width % 8 == 0 && lds % 8 == 0 && ldkv % 8 == 0 && kv_seq_stride % 8 == 0 && src_off >= 0 &&
+                   dst_off >= 0 && src_off % 8 == 0 && dst_off % 8 == 0,
+               "vj_kv_append: width, strides and column offsets must be non-negative multiples of 8");
+  VJ_CHECK_ARG(lds >= (long)src_off + width && ldkv >= (long)dst_off + width,
+               "vj_kv_append: a row stride is shorter than its columns (lds %ld, ldkv %ld, width %d)", lds, ldkv, width);
+  VJ_CHECK_ARG(nseq == 1 || (kv_seq_stride >= ldkv && (long)row0 + nrows <= kv_seq_stride / ldkv),
+               "vj_kv_append: rows %d .. %ld exceed the %ld rows of a sequence's cache slot (kv_seq_stride / ldkv)",
+               row0, (long)row0 + nrows - 1, ldkv ? kv_seq_stride / ldkv : 0L);
+  VJ_CHECK_ARG(((uintptr_t)src | (uintptr_t)kv) % 16 == 0, "vj_kv_append: src and kv must be 16-byte aligned");
+  const int chunks = width / 8;
+  const long total = (long)nseq * nrows * chunks;
+  VJ_CHECK_ARG((total + 255) / 256 <= 0x7fffffffL, "vj_kv_append: too many elements");
+  hipLaunchKernelGGL(k_kv_append, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                     (const bf16_t*)src, lds, src_off, (bf16_t*)kv, kv_seq_stride, ldkv, dst_off, row0, nrows, chunks,
+                     total);
+  VJ_LAUNCH_CHECK("vj_kv_append");
+  return VJ_OK;
 }

@@ -353,6 +353,42 @@ def block_forward(x, blk, lay, save):
     return x_out, saved
 
 
+def cached_block_refusal(blk):
+    """Why block_forward_cached cannot run `blk` (None when it can): the cached forward is the deterministic
+    inference path, so any dropout or drop_path in effect for a call refuses."""
+    if _has_dropout(blk):
+        return "dropout is active (attention / proj / MLP drop probability > 0 in effect for this call)"
+    dp = blk.drop_path
+    if getattr(dp, "drop_prob", None) and dp.training:
+        return "drop_path is active (training mode with drop_path > 0)"
+    if not blk.attn.use_rope:
+        return "the block has no RoPE attention"
+    return None
+
+
+def block_forward_cached(x, blk, lay, kv, row0):
+    """block_forward (inference, no dropout / drop_path) on the rows a rollout step appends: x f32 [S * n, D]
+    holds n new rows of each of S sequences, at positions row0 .. row0 + n - 1. LN1 and QKV + RoPE run on the
+    new rows only (lay: their RoPE ids; lay.fblk: the frame block), their K | V columns are appended to kv
+    (bf16 [S, rows, 2 D], rows below row0 left by earlier calls) and the attention is vj_attn_fwd_kv over
+    rows 0 .. row0 + n - 1 of the cache; proj and the MLP are block_forward's."""
+    T, D = x.shape
+    attn, mlp = blk.attn, blk.mlp
+    H = attn.num_heads
+    hd = D // H
+    n = T // kv.shape[0]
+    ln1, _, _ = ops.layernorm_fwd(x, blk.norm1.weight, blk.norm1.bias, blk.norm1.eps, want_stats=False)
+    c, s = rope_tables(hd, x.device, lay.npos)
+    qkv = ops.qkv_rope(ln1, weight_bf16(attn.qkv.weight), attn.qkv.bias, H, hd, lay.ids, lay.ids_mod, lay.tpf, lay.tpr,
+                       c, s)
+    ops.kv_append(qkv, kv, row0, n, D, 2 * D)
+    o = ops.attn_fwd_kv(qkv, kv, row0 + n, H, hd, _attn_scale(attn, hd, lay), q_pos0=row0, fblk=lay.fblk)
+    x_mid = _branch_out(o, attn.proj, x, None)
+    ln2, _, _ = ops.layernorm_fwd(x_mid, blk.norm2.weight, blk.norm2.bias, blk.norm2.eps, want_stats=False)
+    hidden, out_lin, _ = _mlp_forward(ln2, mlp, False)
+    return _branch_out(hidden, out_lin, x_mid, None)
+
+
 def block_forward_f32(x, blk, lay):
     """fp32-operand parity mode of block_forward: the same LayerNorm / RoPE kernels, f32 MFMA GEMMs
     (vj_gemm_f32) and exact-softmax attention (vj_attn_fwd_f32); every intermediate stays f32."""

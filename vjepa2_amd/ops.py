@@ -509,6 +509,53 @@ def attn_fwd(qkv, H, hd, groups, scale, q_off=None, k_off=None, v_off=None, fblk
     return o, stats
 
 
+def attn_fwd_kv(q, kv, klen, H, hd, scale, q_pos0=0, fblk=0, q_off=0, k_off=0, v_off=None, out=None, stats=None):
+    """New queries over a K/V cache (vj_attn_fwd_kv, inference only). q bf16 [nseq * qlen, ldq] (a QKV GEMM
+    output: the q columns at q_off), kv bf16 [nseq, rows, ldkv] with K at k_off and V at v_off (default H * hd)
+    and the first klen rows of every sequence valid; query i stands at position q_pos0 + i of its sequence and,
+    with fblk > 0, sees key j iff j // fblk <= (q_pos0 + i) // fblk. stats: None, or f32 [H, nseq * qlen] to
+    receive the log2-sum-exp2. Returns O bf16 [nseq * qlen, H * hd]."""
+    _dev(q, kv, out, stats)
+    D = H * hd
+    if q.dtype != BF16 or kv.dtype != BF16 or kv.dim() != 3 or kv.stride(2) != 1:
+        raise TypeError("attn_fwd_kv: q bf16 [nseq * qlen, ldq] and kv bf16 [nseq, rows, ldkv] expected")
+    nseq = kv.shape[0]
+    if q.shape[0] % nseq:
+        raise ValueError(f"attn_fwd_kv: {q.shape[0]} query rows are not a multiple of the cache's {nseq} sequences")
+    qlen = q.shape[0] // nseq
+    if klen > kv.shape[1]:
+        raise ValueError(f"attn_fwd_kv: klen {klen} exceeds the cache's {kv.shape[1]} rows per sequence")
+    v_off = D if v_off is None else v_off
+    o = out if out is not None else torch.empty(q.shape[0], D, dtype=BF16, device=q.device)
+    if stats is not None and (stats.dtype != F32 or stats.shape != (H, q.shape[0]) or not stats.is_contiguous()):
+        raise TypeError("attn_fwd_kv: stats must be contiguous f32 [H, nseq * qlen]")
+    # visible (query, key) pairs x 4 hd flops per head: every earlier block, and the query's own
+    pairs, i = 0.0, 0
+    while i < qlen:
+        n = min(qlen - i, fblk - (q_pos0 + i) % fblk) if fblk else qlen  # queries up to the next block boundary
+        pairs += n * float(min(klen, ((q_pos0 + i) // fblk + 1) * fblk) if fblk else klen)
+        i += n
+    _call("vj_attn_fwd_kv", nseq, qlen, int(klen), H, hd, _p(q), _rowmajor(q, "q"), int(q_off), _p(kv), kv.stride(0),
+          kv.stride(1), int(k_off), int(v_off), _p(o), _rowmajor(o, "o"), _p(stats), float(scale), int(q_pos0),
+          int(fblk), _stream(), label=f"attn_fwd_kv<hd{hd}>", flops=4.0 * nseq * pairs * D)
+    return o
+
+
+def kv_append(src, kv, row0, nrows, src_off, width, dst_off=0):
+    """kv[s, row0:row0 + nrows, dst_off:dst_off + width] = the rows of sequence s of src [nseq * nrows, lds],
+    columns src_off ... (vj_kv_append: the K | V columns of the new rows' QKV projection). Bit-exact."""
+    _dev(src, kv)
+    if src.dtype != BF16 or kv.dtype != BF16 or kv.dim() != 3 or kv.stride(2) != 1:
+        raise TypeError("kv_append: src bf16 [nseq * nrows, lds] and kv bf16 [nseq, rows, ldkv] expected")
+    nseq = kv.shape[0]
+    if src.shape[0] != nseq * nrows or row0 < 0 or row0 + nrows > kv.shape[1]:
+        raise ValueError(f"kv_append: rows {row0} .. {row0 + nrows - 1} of {kv.shape[1]} from {src.shape[0]} source "
+                         f"rows for {nseq} sequences")
+    _call("vj_kv_append", nseq, int(nrows), int(width), _p(src), _rowmajor(src, "src"), int(src_off), _p(kv),
+          kv.stride(0), kv.stride(1), int(dst_off), int(row0), _stream(), label="vj_kv_append")
+    return kv
+
+
 def attn_bwd(qkv, o, do, stats, H, hd, groups, scale, dqkv=None, rope=None, fblk=0, dropout_p=0.0, seed=0):
     """rope = (ids, ids_mod, tpf, tpr, cos_tab, sin_tab) -> dq, dk returned w.r.t. the un-rotated q, k.
     dropout_p, seed: those of the forward (attention dropout)."""

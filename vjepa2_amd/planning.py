@@ -10,7 +10,10 @@ defaults, with everything between two predictor forwards on the device (vj_plan.
    last step) and the next pose into a [S, rollout + 1, 7] pose trajectory (vj_pose_step): no torch.cat, no
    .cpu() / scipy round trip per step;
  * elite selection and the momentum update are one launch (vj_cem_update) on mean / std [rollout, 4] that
-   never leave the device.
+   never leave the device;
+ * opt-in (WorldModel.set_kv_cache(True), not in the reference): rollout step h feeds the predictor frame h
+   alone, the earlier frames' keys and values coming from a per-layer K/V cache (predictor.forward_cached), so
+   a rollout of R steps pushes R frame blocks through the predictor's GEMMs instead of R (R + 1) / 2.
 
 Deliberate difference from the reference: topk < 2 raises ValueError (the reference's unbiased std of a single
 elite is NaN and silently poisons every later sample).
@@ -207,9 +210,25 @@ class _PredictorStep:
         ops.plan_frame(out[:, -1], dst=nxt[:, 0], normalize=self.wm.normalize_reps)
         return nxt, compute_new_pose(poses[:, -1:], actions[:, -1:])
 
+    def _predict_cached(self, traj, h):
+        """The predictor output for frame h alone, [S, HW, D]: frames 0 .. h-1 of this CEM iteration are in the
+        K/V cache (step 0 resets it: its action is resampled every iteration, so nothing carries over)."""
+        S, slots, n_t, D = traj.frames.shape
+        if n_t != self.wm.tokens_per_frame:
+            raise ValueError(f"{n_t} tokens per frame, WorldModel was built for {self.wm.tokens_per_frame}")
+        cache = self.wm._rollout_cache(S, slots - 1)
+        if h == 0:
+            cache.reset()
+        with torch.no_grad():
+            return self.wm.predictor.forward_cached(traj.frames[:, h], traj.actions[:, h:h + 1],
+                                                    traj.poses[:, h:h + 1], cache=cache)
+
     def step_into(self, traj, h, goal):
-        out = self._predict(traj.frames[:, :h + 1], traj.actions[:, :h + 1], traj.poses[:, :h + 1])
-        ops.plan_frame(out[:, -1], goal=goal, dst=traj.frames[:, h + 1], normalize=self.wm.normalize_reps,
+        if self.wm.kv_cache:
+            last = self._predict_cached(traj, h)
+        else:
+            last = self._predict(traj.frames[:, :h + 1], traj.actions[:, :h + 1], traj.poses[:, :h + 1])[:, -1]
+        ops.plan_frame(last, goal=goal, dst=traj.frames[:, h + 1], normalize=self.wm.normalize_reps,
                        energy=traj.energy if goal is not None else None)
         ops.pose_step(traj.poses[:, h], traj.actions[:, h], out=traj.poses[:, h + 1])
         return goal is not None
@@ -245,6 +264,26 @@ class WorldModel(object):
         self.tokens_per_frame = tokens_per_frame
         self.device = device
         self.mpc_args = mpc_args
+        self.kv_cache = False  # set_kv_cache(): the constructor keeps the reference's signature
+        self._cache = None
+
+    def set_kv_cache(self, on=True):
+        """Opt in to (or out of) the K/V cache across rollout steps: infer_next_action's rollout then feeds the
+        predictor one frame per step and keeps the earlier frames' keys and values (predictor.forward_cached)
+        instead of re-running every earlier frame, which is the reference's structure and the default. The
+        generic __call__ path and cem() with a plain callable never cache. Returns self."""
+        self.kv_cache = bool(on)
+        if not self.kv_cache:
+            self._cache = None
+        return self
+
+    def _rollout_cache(self, samples, rollout):
+        """The K/V cache of the planning rollout, allocated once and again only when samples or rollout change."""
+        c = self._cache
+        if c is None or (c.batch, c.max_frames) != (samples, rollout):
+            self._cache = None  # free the old buffers before the new ones are allocated
+            c = self._cache = self.predictor.new_cache(samples, rollout)
+        return c
 
     def encode(self, image):
         clip = np.expand_dims(image, axis=0)
