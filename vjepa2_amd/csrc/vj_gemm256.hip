@@ -170,7 +170,10 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
   // tile, the unit's K offset rides in soffset), 2 per load interval; past the stream end the pieces
   // zero-fill an unread slot, so the per-wave vmcnt count stays 4.
   [[maybe_unused]] const int nku = STG ? (g.K + 31) / 32 : 0;
-  [[maybe_unused]] int dwg = wg, dku = 0, dpos = 0;
+  // The ring position is a running wave-uniform byte offset (ring_step: one add and one wrap per
+  // use): du = the DMA stream's unit slot; the unit to read lies DIST slots behind it. dku = the DMA
+  // stream's unit within its tile (S64: its 64-deep step), whose K offset is the soffset of its pieces.
+  [[maybe_unused]] int dwg = wg, du = 0, dku = 0;
   [[maybe_unused]] __amdgpu_buffer_rsrc_t drs;
   [[maybe_unused]] uint32_t dvo[4];
   const bool isA = wave < 4;
@@ -197,15 +200,14 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       for (int j = 0; j < 4; ++j) dvo[j] = VJ_OOB;
     }
   };
-  // this wave's pieces 2h, 2h + 1 of stream position dpos (into slot dpos % NSL)
+  // this wave's pieces 2h, 2h + 1 of the DMA stream's unit (into the slot at du)
   auto dma_half = [&](auto h_c) {
     constexpr int h = decltype(h_c)::value;
-    LDS_AS char* dst = ring + (dpos % NSL) * USZ + (isA ? 0 : 16384) + (4 * (wave & 3) + 2 * h) * 1024;
-    const int soff = __builtin_amdgcn_readfirstlane(dku * 64);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst, 16, dvo[2 * h], soff, 0, 0);
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst + 1024, 16, dvo[2 * h + 1], soff, 0, 0);
+    LDS_AS char* dst = ring + du + (isA ? 0 : 16384) + (4 * (wave & 3) + 2 * h) * 1024;
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst, 16, dvo[2 * h], dku * 64, 0, 0);
+    __builtin_amdgcn_raw_ptr_buffer_load_lds(drs, dst + 1024, 16, dvo[2 * h + 1], dku * 64, 0, 0);
     if constexpr (h == 1) {
-      ++dpos;
+      du = ring_step<NSL, USZ>(du);
       if (++dku == nku) {
         dku = 0;
         dwg += P;
@@ -213,41 +215,63 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       }
     }
   };
-  // ---- S64 stream: this wave group's operand (A: waves 0-3, B: waves 4-7) as granules; position dq of
-  // the group's stream = (tile, step dk >> 1, half dk & 1), into slot dq % SA (A) / SA + dq % SB (B).
+  // ---- S64 stream: this wave group's operand (A: waves 0-3, B: waves 4-7) as granules; position d of
+  // the group's stream = (tile, step, half h), into slot d % SA (A) / SA + d % SB (B).
   // Each wave DMAs rows 32 (wave & 3) .. + 31 of every granule (4 pieces of 8 rows); its lane offsets
   // are fixed for the launch (rows relative to the granule's first row), the descriptor's range check
-  // (from that row to the operand's end) zero-fills rows past M / N and, past the stream end (dleft 0),
+  // (from that row to the operand's end) zero-fills rows past M / N and, past the stream end (byte count 0),
   // whole granules, so the per-wave vmcnt counts never change.
+  // Both descriptors of a tile (granule halves h = 0 / 1: rows 0-127 / 128-255 of the operand's tile
+  // rows, each with its own clamped byte count) are built once, when the DMA stream enters the tile, and
+  // kept as their six varying words (dlo, dhi, dcnt: two whole descriptors cost two SGPRs more, which
+  // the kernels spill); a granule only picks its half and lines the words up. The position is a
+  // running wave-uniform byte offset (ring_step): dd = the DMA stream's slot within the group's ring.
+  // The two rings have the same size and DMA lead, so in either group the step's A0 and Blo lie EA
+  // slots behind dd of their rings (one add and one wrap each). dku = the DMA stream's step within
+  // its tile, whose K offset is the soffset of the granule's pieces.
+  // A tile has an even number of granules, so the stream alternates h = 0, 1 without exception: the
+  // half is a compile-time argument, and the tile switch can only follow an h = 1 granule.
   [[maybe_unused]] const int nks = S64 ? g.K >> 6 : 0;
-  [[maybe_unused]] const long dld = isA ? g.lda : g.ldb;
-  [[maybe_unused]] const bf16_t* dbase = isA ? g.A : g.B;
-  [[maybe_unused]] int dleft = 0, dq = 0, dk = 0, q64 = 0;
+  [[maybe_unused]] uint32_t dlo[2] = {0, 0}, dhi[2] = {0, 0}, dcnt[2] = {0, 0};
+  [[maybe_unused]] int dd = 0;
+  static_assert(SA == SB && EA == EB, "S64 reads both rings at one offset derived from the DMA slot");
+  [[maybe_unused]] LDS_AS char* const dring = ring + (isA ? 0 : SA * GSZ) + (wave & 3) * 4096;
   auto dma_setup64 = [&]() {
     if (dwg < runend) {
       const Tile T = make_tile(dwg);
-      dbase = isA ? g.A + (long)T.m0 * g.lda : g.B + (long)T.n0 * g.ldb;
-      dleft = isA ? g.M - T.m0 : g.N - T.n0;
-    } else {
-      dleft = 0;
+      const bf16_t* base = isA ? g.A + (long)T.m0 * g.lda : g.B + (long)T.n0 * g.ldb;
+      const int left = isA ? g.M - T.m0 : g.N - T.n0;
+      const long dld = isA ? g.lda : g.ldb;
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        const unsigned long long a = (unsigned long long)(base + h * 128 * dld);
+        dlo[h] = __builtin_amdgcn_readfirstlane((int)(unsigned)a);
+        dhi[h] = __builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32)) & 0xffff;
+        dcnt[h] = __builtin_amdgcn_readfirstlane((int)clampb((long)(left - 128 * h) * dld * 2));
+      }
+    } else {  // past the stream end: empty ranges, every piece zero-fills
+      dcnt[0] = dcnt[1] = 0;
     }
   };
-  auto dma_gran = [&]() {
-    const int h = dk & 1;
-    const __amdgpu_buffer_rsrc_t rs = make_rsrc(dbase + (h ? 128 * dld : 0), clampb((long)(dleft - 128 * h) * dld * 2));
-    const int soff = __builtin_amdgcn_readfirstlane((dk >> 1) * 128);
-    LDS_AS char* dst = ring + (isA ? dq % SA : SA + dq % SB) * GSZ + (wave & 3) * 4096;
+  auto dma_gran = [&](auto h_c) {
+    constexpr int h = decltype(h_c)::value;
+    LDS_AS char* dst = dring + dd;
+    const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(dlo[h] | ((unsigned long long)dhi[h] << 32)), (short)0, (int)dcnt[h], 0x00020000);  // as make_rsrc
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + k * 1024, 16, dvo[k], soff, 0, 0);
-    ++dq;
-    if (++dk == 2 * nks) {
-      dk = 0;
-      dwg += P;
-      dma_setup64();
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, dst + k * 1024, 16, dvo[k], dku * 128, 0, 0);
+    dd = ring_step<SA, GSZ>(dd);
+    if constexpr (h == 1) {
+      if (++dku == nks) {
+        dku = 0;
+        dwg += P;
+        dma_setup64();
+      }
     }
   };
   if constexpr (S64) {
+    const long dld = isA ? g.lda : g.ldb;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const int r = 32 * (wave & 3) + 8 * k + (lane >> 3);  // granule row of the lane's 16-B chunk
@@ -257,7 +281,12 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       dvo[k] = (uint32_t)(gr * dld * 2 + c * 16);
     }
     dma_setup64();
-    for (int i = 0; i < (isA ? EA : EB); ++i) dma_gran();
+#pragma unroll
+    for (int i = 0; i < cmax(EA, EB); ++i)
+      if (i < (isA ? EA : EB)) {
+        if (i & 1) dma_gran(std::integral_constant<int, 1>{});
+        else dma_gran(std::integral_constant<int, 0>{});
+      }
   } else if constexpr (STG) {
     dma_setup();
 #pragma unroll
@@ -508,7 +537,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
           for (int j = 0; j < 4; ++j)
             acc[4 * h + i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(Ab[i], Bb[j], acc[4 * h + i][j], 0, 0, 0);
       };
-      const int qt = q64;  // stream position of this tile's A0 / Blo of step 0
 #if VJ_GEMM_STAMPS
       long* ist = (stamp_it == 1 && (wave & 3) == 0 && lane == 0 && blockIdx.x < 2048)
                       ? vj_gemm_istamps + ((long)blockIdx.x * 2 + (wave >> 2)) * 16 : nullptr;
@@ -519,10 +547,9 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
       auto istamp = [](int, int) {};
 #endif
       for (int s = 0; s < nks; ++s) {
-        const int p = qt + 2 * s;
-        const LDS_AS char* sA0 = ring + (p % SA) * GSZ;
-        const LDS_AS char* sA1 = ring + ((p + 1) % SA) * GSZ;
-        const LDS_AS char* sB = ring + (SA + (p + (wc >> 1)) % SB) * GSZ;
+        const LDS_AS char* sA0 = ring + ring_step<SA, GSZ>(dd, SA - EA);
+        const LDS_AS char* sA1 = ring + ring_step<SA, GSZ>(dd, SA - EA + 1);
+        const LDS_AS char* sB = ring + SA * GSZ + ring_step<SB, GSZ>(dd, SB - EB + (wc >> 1));
         const bool last = s + 1 == nks;
         // L0
 #pragma unroll
@@ -533,7 +560,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         for (int i = 0; i < 4; ++i) Ab[i] = frag<true, 128, 64>(sA0, wr * 64 + i * 16, 1, lane);
 #pragma unroll
         for (int j = 0; j < 4; ++j) Bb[j] = frag<true, 128, 64>(sB, (wc & 1) * 64 + j * 16, 1, lane);
-        dma_gran();
+        dma_gran(std::integral_constant<int, EA & 1>{});
         if (isA) vm_wait<4 * (EA - 1)>();
         if (AUX && last) stg_aux();
         bar();
@@ -546,7 +573,7 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         for (int i = 0; i < 4; ++i) Aa[i] = frag<true, 128, 64>(sA1, wr * 64 + i * 16, 0, lane);
 #pragma unroll
         for (int i = 0; i < 4; ++i) Ab[i] = frag<true, 128, 64>(sA1, wr * 64 + i * 16, 1, lane);
-        dma_gran();
+        dma_gran(std::integral_constant<int, (EA & 1) ^ 1>{});
         // counts: pieces issued after the awaited granule (+ 4 aux loads in the last step)
         constexpr int WA = 4 * (EA - 1), WB = 4 * (EB - 2);
         if (AUX && last) {
@@ -565,7 +592,6 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         if (!last || wr == 0) bar();
         istamp(s, 3);
       }
-      q64 = qt + 2 * nks;
     } else if constexpr (STG) {
       // Staggered main loop. Per unit, each wave runs L | M (intervals between workgroup
       // barriers): L = the unit's fragment reads (A m-tiles 0-7, B n-tiles 0-3: 12 ds_read_b128) + its
@@ -584,14 +610,13 @@ __global__ __launch_bounds__(NWV * 64, 2) void k_gemm256(G256 g) {
         __builtin_amdgcn_s_barrier();
         if (wr == 1) __builtin_amdgcn_s_barrier();
       }
-      const int q0 = dpos - DIST;  // stream position of this tile's unit 0
       auto bar = [] {
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
       };
       for (int u = 0; u < nku; ++u) {
-        const LDS_AS char* sA = ring + ((q0 + u) % NSL) * USZ;
+        const LDS_AS char* sA = ring + ring_step<NSL, USZ>(du, NSL - DIST);  // DIST slots behind the DMA
         const LDS_AS char* sB = sA + 16384;
 #pragma unroll
         for (int i = 0; i < 4; ++i) Aa[i] = frag<true, 256, 32>(sA, wr * 128 + i * 16, 0, lane);

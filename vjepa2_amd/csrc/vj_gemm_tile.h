@@ -51,6 +51,17 @@ __device__ __forceinline__ uint32_t clampb(long b) {
   return b > 0x7fffffffL ? 0x7fffffffu : (uint32_t)b;
 }
 
+// Byte offset of a slot in a ring of S slots of SZ bytes, n <= S slots after the slot at byte offset x:
+// one add and one wrap (a mask where the ring's byte size is a power of two, else a compare-select).
+// The staggered main loops keep their LDS positions as such running wave-uniform offsets.
+template <int S, int SZ>
+__device__ __forceinline__ int ring_step(int x, int n = 1) {
+  constexpr int R = S * SZ;
+  if constexpr ((R & (R - 1)) == 0) return (x + n * SZ) & (R - 1);
+  x += n * SZ;
+  return x >= R ? x - R : x;
+}
+
 __device__ __forceinline__ int mn_swz(int k) { return 2 * (k & 3) + 8 * ((k >> 3) & 1); }
 
 // 64-B K-major rows (32-deep K tiles): the 16-B chunk swizzle. A 16x16x32 fragment read (row rb + (l &
