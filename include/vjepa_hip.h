@@ -161,6 +161,17 @@ int vj_layernorm_fwd_fp8(int M, int D, const void* x, int x_bf16, long ldx, cons
  * gamma/beta optional (both or neither); mean/rstd optional outputs. D % 4 == 0, D <= 2048. */
 int vj_layernorm_fwd(int M, int D, const void* x, int x_bf16, long ldx, const float* gamma, const float* beta,
                      float eps, void* y, int y_f32, long ldy, float* mean, float* rstd, void* stream);
+/* LayerNorm of the tapped layers of a multilevel eval encoder, written once where the probe reads them
+ * (evals/video_classification_frozen/modelcustom/vit_encoder_multiclip_multilevel.py: norm per tapped
+ * layer, cat over levels, per-view slice / reshape / cat). x f32 or bf16 [G*n][ldx]: group g is rows
+ * [g*n, (g+1)*n). Group g is written, f32, to out rows [dst_block[g]*n, dst_block[g]*n + n) of out
+ * [R_out][ldo]; no other row and no column >= D of out is touched. dst_block int32 [G] on the device: the
+ * caller guarantees distinct values in [0, R_out / n); the kernel decides the destination per row and
+ * writes nothing for a value outside that range. The row arithmetic (and the kernel choice by dtype,
+ * stride and alignment) is vj_layernorm_fwd's with y_f32 = 1: results are bit-identical. G, n >= 1,
+ * D % 4 == 0, D <= 2048, ldx, ldo >= D and % 4, G*n and R_out within int, x / out / gamma / beta 16-B aligned. */
+int vj_layernorm_taps(int G, int n, int D, const void* x, int x_bf16, long ldx, const float* gamma, const float* beta,
+                      float eps, float* out, long ldo, long R_out, const int* dst_block, void* stream);
 /* Backward (dy bf16): dres(f32) = (dres_in or 0) + dx; optional bf16 copy of dres; dgamma/dbeta
  * accumulated (+=) through a workspace of vj_layernorm_bwd_blocks(M)*2*D floats. Optional sum_in / sum_out
  * (+=) column sums of dres_in / dres (the fc2 / proj bias gradients, modules.py:77-83, 326-382); with

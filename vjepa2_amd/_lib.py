@@ -42,6 +42,7 @@ SIGNATURES = {
     "vj_kv_append": [_I, _I, _I, _P, _L, _I, _P, _L, _L, _I, _I, _P],
     "vj_qkv_rope_gemm": [_I, _I, _P, _L, _P, _L, _P, _P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P],
     "vj_layernorm_fwd": [_I, _I, _P, _I, _L, _P, _P, _F, _P, _I, _L, _P, _P, _P],
+    "vj_layernorm_taps": [_I, _I, _I, _P, _I, _L, _P, _P, _F, _P, _L, _L, _P, _P],
     "vj_gemm_fp8": [_I, _I, _I, _P, _L, _P, _P, _L, _P, _I, _P, _P, _L, _P, _L, _P, _L, _P],
     "vj_qkv_rope_gemm_fp8": [_I, _I, _P, _L, _P, _P, _L, _P, _P, _P, _L, _I, _I, _P, _I, _I, _I, _P, _P, _I, _P],
     "vj_quant_rows_fp8": [_I, _I, _P, _I, _L, _P, _L, _P, _P],

@@ -9,6 +9,8 @@
 //   fused target-LN + L1 loss   forward_target F.layer_norm + loss_fn (app/vjepa/train.py:414-435)
 //   AdamW, finite-check, EMA    torch.optim.AdamW foreach math (app/vjepa/utils.py:239), train.py:456-465
 //   column sums (bias grads), f32->bf16 casts
+#include <climits>
+
 #include "vj_common.h"
 
 static_assert(sizeof(float4) == 16, "");
@@ -50,11 +52,27 @@ __device__ __forceinline__ void ln_load_row(const void* __restrict__ x, long ldx
   }
 }
 
-template <bool XBF, bool YF32, int NV, bool YF8 = false>
+// TAP (vj_layernorm_taps): input row r of group r / tap_n goes to output row dst_block[r / tap_n] * tap_n +
+// r % tap_n, decided per row (a wave's rows may straddle a group boundary); a block id outside
+// [0, tap_blocks) writes nothing. The row arithmetic is the same code either way.
+template <bool TAP>
+__device__ __forceinline__ long ln_out_row(long row, int tap_n, const int* __restrict__ dst_block, int tap_blocks) {
+  if constexpr (TAP) {
+    const int g = (int)row / tap_n;
+    const int b = dst_block[g];
+    return (unsigned)b < (unsigned)tap_blocks ? (long)b * tap_n + ((int)row - g * tap_n) : -1;
+  } else {
+    return row;
+  }
+}
+
+template <bool XBF, bool YF32, int NV, bool YF8 = false, bool TAP = false>
 __global__ __launch_bounds__(256) void k_ln_fwd(int M, int D, const void* __restrict__ x, long ldx,
                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                 float eps, void* __restrict__ y, long ldy, float* __restrict__ mean,
-                                                float* __restrict__ rstd, int* __restrict__ yexp = nullptr) {
+                                                float* __restrict__ rstd, int* __restrict__ yexp = nullptr,
+                                                int tap_n = 0, const int* __restrict__ dst_block = nullptr,
+                                                int tap_blocks = 0) {
   const int lane = threadIdx.x & 63;
   const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * LN_RPW;
   if (row0 >= M) return;
@@ -89,10 +107,11 @@ __global__ __launch_bounds__(256) void k_ln_fwd(int M, int D, const void* __rest
       }
     }
     const float rs = rsqrtf(wave_sum(q) / D + eps);
+    const long orow = ln_out_row<TAP>(row, tap_n, dst_block, tap_blocks);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      if (c < D) {
+      if (c < D && (!TAP || orow >= 0)) {
         float o[4] = {(v[i].x - mu) * rs, (v[i].y - mu) * rs, (v[i].z - mu) * rs, (v[i].w - mu) * rs};
         if (gamma) {
           o[0] = o[0] * g[i].x + bb[i].x; o[1] = o[1] * g[i].y + bb[i].y;
@@ -101,9 +120,9 @@ __global__ __launch_bounds__(256) void k_ln_fwd(int M, int D, const void* __rest
         if constexpr (YF8) {
           v[i] = make_float4(o[0], o[1], o[2], o[3]);  // kept for the scaled fp8 pass below
         } else if constexpr (YF32) {
-          *(float4*)((float*)y + row * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
+          *(float4*)((float*)y + orow * ldy + c) = make_float4(o[0], o[1], o[2], o[3]);
         } else {
-          *(uint2*)((bf16_t*)y + row * ldy + c) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
+          *(uint2*)((bf16_t*)y + orow * ldy + c) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
         }
       }
     }
@@ -141,11 +160,12 @@ __global__ __launch_bounds__(256) void k_ln_fwd(int M, int D, const void* __rest
 // a lower register cost (bf16 rows stay packed: 8 VGPRs per 1024-wide row). Element map: vector i of
 // lane l holds elements (64 i + l) E ... + E - 1. Outputs: bf16 rows as 16-B (E = 8) / 8-B stores,
 // f32 rows as 16-B stores; gamma / beta re-read per row (L1 hits) instead of held in registers.
-template <bool XBF, bool YF32, int NV, int R>
+template <bool XBF, bool YF32, int NV, int R, bool TAP = false>
 __global__ __launch_bounds__(256) void k_ln_fwd3(int M, int D, const void* __restrict__ x, long ldx,
                                                  const float* __restrict__ gamma, const float* __restrict__ beta,
                                                  float eps, void* __restrict__ y, long ldy, float* __restrict__ mean,
-                                                 float* __restrict__ rstd) {
+                                                 float* __restrict__ rstd, int tap_n = 0,
+                                                 const int* __restrict__ dst_block = nullptr, int tap_blocks = 0) {
   constexpr int E = XBF ? 8 : 4;
   const int lane = threadIdx.x & 63;
   const long row0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * R;
@@ -197,9 +217,10 @@ __global__ __launch_bounds__(256) void k_ln_fwd3(int M, int D, const void* __res
           q += a * a;
         }
     const float rs = rsqrtf(wave_sum(q) / D + eps);
+    const long orow = ln_out_row<TAP>(row, tap_n, dst_block, tap_blocks);
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
-      if (!ok(i)) continue;
+      if (!ok(i) || (TAP && orow < 0)) continue;
       const int c = (i * 64 + lane) * E;
       float o[E];
 #pragma unroll
@@ -212,7 +233,7 @@ __global__ __launch_bounds__(256) void k_ln_fwd3(int M, int D, const void* __res
           o[k + 2] = o[k + 2] * gg.z + bb.z; o[k + 3] = o[k + 3] * gg.w + bb.w;
         }
       }
-      const long off = row * ldy + c;
+      const long off = orow * ldy + c;
       if constexpr (YF32) {
 #pragma unroll
         for (int k = 0; k < E; k += 4) *(float4*)((float*)y + off + k) = make_float4(o[k], o[k + 1], o[k + 2], o[k + 3]);
@@ -1106,14 +1127,12 @@ static int ln_nv(int D) {  // float4 per lane for a row of D floats (templated r
   return v <= 1 ? 1 : v <= 2 ? 2 : v <= 4 ? 4 : v <= 6 ? 6 : 8;
 }
 
-extern "C" int vj_layernorm_fwd(int M, int D, const void* x, int x_bf16, long ldx, const float* gamma,
-                                const float* beta, float eps, void* y, int y_f32, long ldy, float* mean, float* rstd,
-                                void* stream) {
-  if (M == 0) return VJ_OK;
-  VJ_CHECK_ARG(D % 4 == 0 && D <= 64 * 4 * LN_MAXV, "vj_layernorm_fwd: D=%d must be %%4 and <= 2048", D);
-  VJ_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "vj_layernorm_fwd: gamma/beta both or neither");
-  VJ_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0, "vj_layernorm_fwd: strides must be %%4");
-  hipStream_t st = (hipStream_t)stream;
+// The forward dispatch shared by vj_layernorm_fwd and vj_layernorm_taps (dst_block != nullptr: f32 output
+// rows placed by group, see ln_out_row), so that both pick the same kernel, hence the same row
+// arithmetic, for the same input.
+static int ln_fwd_dispatch(const char* what, int M, int D, const void* x, int x_bf16, long ldx, const float* gamma,
+                           const float* beta, float eps, void* y, int y_f32, long ldy, float* mean, float* rstd,
+                           int tap_n, const int* dst_block, int tap_blocks, hipStream_t st) {
   // k_ln_fwd3 (all rows of a wave in flight, 16-B accesses) for bf16 inputs where the row fits its
   // register budget and the strides allow 16-B vectors; else the one-row-lookahead k_ln_fwd.
   // Measured (profiles/r04_ln_fwd_kernels.txt): bf16 target rows 42.3 -> 37.6 us, but f32 rows (the
@@ -1129,28 +1148,73 @@ extern "C" int vj_layernorm_fwd(int M, int D, const void* x, int x_bf16, long ld
     constexpr int R = 4;
     dim3 grid((M + 4 * R - 1) / (4 * R));
 #define LNF(XB, YF, NVV) hipLaunchKernelGGL((k_ln_fwd3<XB, YF, NVV, R>), grid, dim3(256), 0, st, M, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd)
+#define LNT(XB, NVV) hipLaunchKernelGGL((k_ln_fwd3<XB, true, NVV, R, true>), grid, dim3(256), 0, st, M, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, tap_n, dst_block, tap_blocks)
 #define LNF_NV(XB, YF) switch (nv3) { case 1: LNF(XB, YF, 1); break; case 2: LNF(XB, YF, 2); break; case 3: LNF(XB, YF, 3); break; default: LNF(XB, YF, 4); }
-    if (x_bf16 && y_f32) { LNF_NV(true, true) }
+#define LNT_NV(XB) switch (nv3) { case 1: LNT(XB, 1); break; case 2: LNT(XB, 2); break; case 3: LNT(XB, 3); break; default: LNT(XB, 4); }
+    if (dst_block && x_bf16) { LNT_NV(true) }
+    else if (dst_block) { LNT_NV(false) }
+    else if (x_bf16 && y_f32) { LNF_NV(true, true) }
     else if (x_bf16) { LNF_NV(true, false) }
     else if (y_f32) { LNF_NV(false, true) }
     else { LNF_NV(false, false) }
+#undef LNT_NV
 #undef LNF_NV
+#undef LNT
 #undef LNF
-    VJ_LAUNCH_CHECK("vj_layernorm_fwd");
+    VJ_LAUNCH_CHECK(what);
     return VJ_OK;
   }
   dim3 grid((M + 4 * LN_RPW - 1) / (4 * LN_RPW));
   const int nv = ln_nv(D);
 #define LNF(XB, YF, NVV) hipLaunchKernelGGL((k_ln_fwd<XB, YF, NVV>), grid, dim3(256), 0, st, M, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd)
+#define LNT(XB, NVV) hipLaunchKernelGGL((k_ln_fwd<XB, true, NVV, false, true>), grid, dim3(256), 0, st, M, D, x, ldx, gamma, beta, eps, y, ldy, mean, rstd, (int*)nullptr, tap_n, dst_block, tap_blocks)
 #define LNF_NV(XB, YF) switch (nv) { case 1: LNF(XB, YF, 1); break; case 2: LNF(XB, YF, 2); break; case 4: LNF(XB, YF, 4); break; case 6: LNF(XB, YF, 6); break; default: LNF(XB, YF, 8); }
-  if (x_bf16 && y_f32) { LNF_NV(true, true) }
+#define LNT_NV(XB) switch (nv) { case 1: LNT(XB, 1); break; case 2: LNT(XB, 2); break; case 4: LNT(XB, 4); break; case 6: LNT(XB, 6); break; default: LNT(XB, 8); }
+  if (dst_block && x_bf16) { LNT_NV(true) }
+  else if (dst_block) { LNT_NV(false) }
+  else if (x_bf16 && y_f32) { LNF_NV(true, true) }
   else if (x_bf16) { LNF_NV(true, false) }
   else if (y_f32) { LNF_NV(false, true) }
   else { LNF_NV(false, false) }
+#undef LNT_NV
 #undef LNF_NV
+#undef LNT
 #undef LNF
-  VJ_LAUNCH_CHECK("vj_layernorm_fwd");
+  VJ_LAUNCH_CHECK(what);
   return VJ_OK;
+}
+
+extern "C" int vj_layernorm_fwd(int M, int D, const void* x, int x_bf16, long ldx, const float* gamma,
+                                const float* beta, float eps, void* y, int y_f32, long ldy, float* mean, float* rstd,
+                                void* stream) {
+  if (M == 0) return VJ_OK;
+  VJ_CHECK_ARG(D % 4 == 0 && D <= 64 * 4 * LN_MAXV, "vj_layernorm_fwd: D=%d must be %%4 and <= 2048", D);
+  VJ_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "vj_layernorm_fwd: gamma/beta both or neither");
+  VJ_CHECK_ARG(ldx % 4 == 0 && ldy % 4 == 0, "vj_layernorm_fwd: strides must be %%4");
+  return ln_fwd_dispatch("vj_layernorm_fwd", M, D, x, x_bf16, ldx, gamma, beta, eps, y, y_f32, ldy, mean, rstd, 0,
+                         nullptr, 0, (hipStream_t)stream);
+}
+
+// LayerNorm of G groups of n rows whose f32 output rows are placed by group (the multilevel eval
+// wrapper's tapped layers, written once into the buffer the classifiers read): see include/vjepa_hip.h.
+extern "C" int vj_layernorm_taps(int G, int n, int D, const void* x, int x_bf16, long ldx, const float* gamma,
+                                 const float* beta, float eps, float* out, long ldo, long R_out,
+                                 const int* dst_block, void* stream) {
+  VJ_CHECK_ARG(x && out && dst_block, "vj_layernorm_taps: null operand");
+  VJ_CHECK_ARG((gamma == nullptr) == (beta == nullptr), "vj_layernorm_taps: gamma/beta both or neither");
+  VJ_CHECK_ARG(G >= 1 && n >= 1, "vj_layernorm_taps: G and n must be >= 1 (got %d, %d)", G, n);
+  VJ_CHECK_ARG(D >= 4 && D % 4 == 0 && D <= 64 * 4 * LN_MAXV, "vj_layernorm_taps: D=%d must be %%4 and in [4, 2048]",
+               D);
+  VJ_CHECK_ARG((long)G * n <= INT_MAX, "vj_layernorm_taps: G * n = %ld rows exceed int range", (long)G * n);
+  VJ_CHECK_ARG(R_out >= 0 && R_out <= INT_MAX, "vj_layernorm_taps: R_out = %ld rows exceed int range", R_out);
+  VJ_CHECK_ARG(R_out / n >= G, "vj_layernorm_taps: out has %ld blocks of %d rows for %d groups", R_out / n, n, G);
+  VJ_CHECK_ARG(ldx >= D, "vj_layernorm_taps: ldx %ld < D %d", ldx, D);
+  VJ_CHECK_ARG(ldo >= D, "vj_layernorm_taps: out stride %ld < D %d", ldo, D);
+  VJ_CHECK_ARG(ldx % 4 == 0 && ldo % 4 == 0, "vj_layernorm_taps: strides must be %%4 (16-B row vectors)");
+  VJ_CHECK_ARG(!((uintptr_t)x & 15) && !((uintptr_t)out & 15) && !((uintptr_t)gamma & 15) && !((uintptr_t)beta & 15),
+               "vj_layernorm_taps: x, out, gamma and beta must be 16-B aligned");
+  return ln_fwd_dispatch("vj_layernorm_taps", G * n, D, x, x_bf16, ldx, gamma, beta, eps, out, 1, ldo, nullptr,
+                         nullptr, n, dst_block, (int)(R_out / n), (hipStream_t)stream);
 }
 
 extern "C" int vj_layernorm_bwd_blocks(int M) {

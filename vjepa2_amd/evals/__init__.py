@@ -4,7 +4,8 @@ import importlib
 
 # eval_name -> module under this package (the reference imports evals.<eval_name>.eval)
 EVALS = {"video_classification_frozen": "video_classification_frozen",
-         "action_anticipation_frozen": "action_anticipation_frozen"}
+         "action_anticipation_frozen": "action_anticipation_frozen",
+         "image_classification_frozen": "image_classification_frozen"}
 
 
 def main(eval_name, args_eval, resume_preempt=False):

@@ -1,6 +1,7 @@
 """Frozen-encoder video-classification probe (drop-in for evals/video_classification_frozen/eval.py and
-its modelcustom/vit_encoder_multiclip.py:41-78 init_module): the SSv2 / K400 / Diving48 / Jester / COIN
-configs of configs/eval/.
+its modelcustom/vit_encoder_multiclip.py:41-78 and vit_encoder_multiclip_multilevel.py:41-82 init_module):
+the SSv2 / K400 / COIN configs of configs/eval/ (single-level wrapper) and the Diving48 / Jester ones
+(multilevel wrapper: four tapped layers, each normed once into the classifiers' buffer by vj_layernorm_taps).
 
 `main(args_eval, resume_preempt)` reads the reference's config keys (eval.py:48-108) and runs its epoch
 (eval.py:283-356): frozen encoder forward -> every attentive classifier on every view -> per-view
@@ -39,13 +40,14 @@ from .. import vision_transformer as vit
 from ..arena import FlatArena, FusedAdamW, readiness_order
 from ..attentive_pooler import AttentiveClassifier
 from ..functions import join_wgrad_stream, refresh_weight_transposes
-from ..multiclip import ClipAggregation
+from ..multiclip import ClipAggregation, ClipAggregationMultilevel
 from ..train import GradScalerFlag, SyntheticLabelledVideoDataset
 
 logger = logging.getLogger(__name__)
 _GLOBAL_SEED = 0
 _MC_KEYS = ("mc_warmup_steps", "mc_start_lr", "mc_ref_lr", "mc_final_lr", "mc_ref_wd", "mc_final_wd")
 MULTICLIP_MODULE = "evals.video_classification_frozen.modelcustom.vit_encoder_multiclip"
+MULTILEVEL_MODULE = "evals.video_classification_frozen.modelcustom.vit_encoder_multiclip_multilevel"
 
 
 # ------------------------------------------------------------------------------------------------
@@ -176,6 +178,11 @@ class ProbeTrainer:
         self.on_grads = None
 
     def _tokens(self, clips, clip_indices):
+        stacked = getattr(self.encoder, "forward_stacked", None)
+        if stacked is not None:  # the multilevel wrapper writes the views into one buffer: no cat
+            with torch.no_grad():
+                x, V = stacked(clips, clip_indices)
+            return x.detach(), V
         with torch.no_grad():
             outputs = self.encoder(clips, clip_indices)
         V = len(outputs)
@@ -263,11 +270,17 @@ def _strip(sd):
 def init_module(module_name, frames_per_clip, resolution, checkpoint, model_kwargs, wrapper_kwargs, device):
     """evals/video_classification_frozen/models.py + modelcustom/vit_encoder_multiclip.py:41-78: the HIP
     VisionTransformer `model_name`, weights from checkpoint[checkpoint_key] (non-strict, DDP / wrapper
-    prefixes stripped), wrapped in ClipAggregation; frozen, in eval mode, on `device`."""
-    if module_name is not None and module_name != MULTICLIP_MODULE:
-        raise NotImplementedError(f"encoder module {module_name!r}: only {MULTICLIP_MODULE} is ported")
+    prefixes stripped), wrapped in ClipAggregation; frozen, in eval mode, on `device`. With the module
+    name of modelcustom/vit_encoder_multiclip_multilevel.py:41-82 (Diving48, Jester) the encoder is built
+    with wrapper_kwargs["out_layers"] and wrapped in ClipAggregationMultilevel."""
+    multilevel = module_name == MULTILEVEL_MODULE
+    if module_name is not None and module_name != MULTICLIP_MODULE and not multilevel:
+        raise NotImplementedError(f"encoder module {module_name!r}: only {MULTICLIP_MODULE} and "
+                                  f"{MULTILEVEL_MODULE} are ported")
     enc_kwargs = dict(model_kwargs["encoder"])
     ckp_key = enc_kwargs.get("checkpoint_key")
+    if multilevel:
+        enc_kwargs["out_layers"] = (wrapper_kwargs or {}).get("out_layers")
     model = vit.__dict__[enc_kwargs.get("model_name")](img_size=resolution, num_frames=frames_per_clip, **enc_kwargs)
     logger.info("Loading pretrained model from %s", checkpoint)
     ck = torch.load(checkpoint, map_location="cpu", weights_only=True)
@@ -281,7 +294,8 @@ def init_module(module_name, frames_per_clip, resolution, checkpoint, model_kwar
     msg = model.load_state_dict(pretrained, strict=False)
     logger.info("loaded pretrained model with msg: %s", msg)
     del ck
-    model = ClipAggregation(model, tubelet_size=model.tubelet_size, **(wrapper_kwargs or {}))
+    wrap = ClipAggregationMultilevel if multilevel else ClipAggregation
+    model = wrap(model, tubelet_size=model.tubelet_size, **(wrapper_kwargs or {}))
     model = model.to(device).eval()
     for p in model.parameters():
         p.requires_grad = False

@@ -381,6 +381,67 @@ def layernorm_fwd(x, weight, bias, eps, out_dtype=BF16, want_stats=True):
     return y, mean, rstd
 
 
+_TAP_BLOCKS = {}  # (device, blocks of out, dst_block values) -> the validated device copy
+
+
+def tap_blocks(dst_block, nblocks, device):
+    """The device copy (int32 [G]) of a layernorm_taps destination map, built by host code from shapes:
+    checked here, on the host, to be distinct values in [0, nblocks), and cached per (device, nblocks,
+    values) so a repeated shape costs no upload."""
+    vals = tuple(int(v) for v in dst_block)
+    key = (str(device), int(nblocks), vals)
+    t = _TAP_BLOCKS.get(key)
+    if t is None:
+        if not vals:
+            raise ValueError("layernorm_taps: empty dst_block")
+        if min(vals) < 0 or max(vals) >= nblocks:
+            bad = min(vals) if min(vals) < 0 else max(vals)
+            raise IndexError(f"layernorm_taps: dst_block value {bad} out of range for {nblocks} blocks of out")
+        if len(set(vals)) != len(vals):
+            raise ValueError("layernorm_taps: dst_block repeats a destination block (groups would overwrite each other)")
+        if torch.device(device).type != "cuda":
+            raise RuntimeError("vjepa2_amd ops require device (HIP) tensors; there is no CPU path")
+        if len(_TAP_BLOCKS) >= 256:
+            _TAP_BLOCKS.clear()
+        t = _TAP_BLOCKS[key] = torch.tensor(vals, dtype=torch.int32, device=device)
+    return t
+
+
+def layernorm_taps(x, weight, bias, eps, out, n, dst_block):
+    """LayerNorm of G groups of n rows, written f32 where a multilevel probe reads them (vj_layernorm_taps).
+
+    x f32 or bf16 [G*n, D] (row stride >= D): group g is rows [g*n, (g+1)*n). out f32 [R_out, D] (row stride
+    >= D). dst_block: a host sequence (or CPU integer tensor) of G distinct block ids in [0, R_out // n);
+    group g goes to out rows [dst_block[g]*n, dst_block[g]*n + n). Nothing else of out is written. A row
+    equals ops.layernorm_fwd(x, ..., out_dtype=float32, want_stats=False) bit for bit. Dtypes, shapes and
+    the map are checked first, on the host; then the operands must be on the device."""
+    if x.dtype not in (F32, BF16):
+        raise TypeError(f"layernorm_taps: x must be f32 or bf16, got {x.dtype}")
+    if out.dtype != F32:
+        raise TypeError(f"layernorm_taps: out must be f32, got {out.dtype}")
+    if weight.dtype != F32 or bias.dtype != F32:
+        raise TypeError("layernorm_taps: weight and bias must be f32")
+    ldx, ldo = _rowmajor(x, "x"), _rowmajor(out, "out")
+    M, D = x.shape
+    n = int(n)
+    if n < 1 or M < n or M % n != 0:
+        raise ValueError(f"layernorm_taps: {M} rows are not whole groups of n={n}")
+    if out.shape[1] != D or weight.numel() != D or bias.numel() != D:
+        raise ValueError(f"layernorm_taps: x is {D} wide, out {out.shape[1]}, weight {weight.numel()}, bias {bias.numel()}")
+    if isinstance(dst_block, torch.Tensor):
+        if dst_block.is_cuda or dst_block.is_floating_point():
+            raise TypeError("layernorm_taps: dst_block is a host sequence of ints (it is validated before upload)")
+        dst_block = dst_block.reshape(-1).tolist()
+    G, R_out = M // n, out.shape[0]
+    if len(dst_block) != G:
+        raise ValueError(f"layernorm_taps: {len(dst_block)} destination blocks for {G} groups")
+    blocks = tap_blocks(dst_block, R_out // n, x.device)
+    _dev(x, out, weight, bias)
+    _call("vj_layernorm_taps", G, n, D, _p(x), int(x.dtype == BF16), ldx, _p(weight), _p(bias), float(eps), _p(out), ldo,
+          R_out, _p(blocks), _stream())
+    return out
+
+
 def layernorm_bwd(dy, x, mean, rstd, weight, dres_in=None, dweight=None, dbias=None, want_bf16=False, sum_in=None,
                   sum_out=None):
     """Returns (dres f32 = dres_in + dLN/dx, optional bf16 copy). Accumulates dweight/dbias and the

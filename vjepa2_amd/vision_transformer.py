@@ -215,6 +215,34 @@ class VisionTransformer(nn.Module):
             t = fn.run_layernorm(t, self.norm)
         return self._reshape(t, lay)
 
+    def tap_layers(self):
+        """The tapped blocks in the order forward() emits them (vision_transformer.py:203-205: block order)."""
+        taps = self.out_layers if self.out_layers is not None else ()
+        return [i for i in range(len(self.blocks)) if i in taps]
+
+    @torch.no_grad()
+    def forward_taps(self, x, out, dst_blocks):
+        """forward() of a frozen model with out_layers, each tapped layer's norm written once into `out`
+        (f32 [R_out, D], row stride >= D) instead of returned: after the l-th tapped block, sample g's N
+        tokens go to out rows [dst_blocks[l][g] * N, ... + N) (ops.layernorm_taps with the shared final
+        norm). The blocks run on the f32 residual stream exactly as in forward(), so a row equals
+        forward()'s bit for bit; blocks after the last tap cannot change the result and are not run.
+        No autograd (the eval encoders are frozen). Returns (tokens per sample N, number of taps)."""
+        taps = self.tap_layers()
+        if not taps:
+            raise ValueError("forward_taps needs a model built with out_layers that name at least one of its blocks")
+        if len(dst_blocks) != len(taps):
+            raise ValueError(f"{len(dst_blocks)} destination maps for {len(taps)} tapped layers")
+        t, lay = self.tokens(x, None)
+        N = lay.groups[0][1]
+        level = 0
+        for i, blk in enumerate(self.blocks[:taps[-1] + 1]):
+            t = fn.run_block(t, blk, lay)
+            if i == taps[level]:
+                ops.layernorm_taps(t, self.norm.weight, self.norm.bias, self.norm.eps, out, N, dst_blocks[level])
+                level += 1
+        return N, len(taps)
+
     @torch.no_grad()
     def forward_fp32(self, x, masks=None):
         """fp32-operand parity mode of forward(): f32 operands and intermediates throughout (f32 MFMA
