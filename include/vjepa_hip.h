@@ -415,6 +415,30 @@ int vj_cem_update(int S, int rollout, int k, const float* energy, const float* a
                   double momentum_std, double momentum_mean_gripper, double momentum_std_gripper, float* mean,
                   float* std, int* elite_idx, void* stream);
 
+/* V-JEPA 2-AC post-training, the loss side of one step (vj_acloss.hip; app/vjepa_droid/train.py
+ * forward_predictions / loss_fn and their autograd). Rows [B][R][D] of f32: z at z + b * z_sample_stride + r *
+ * z_row_stride (a frame slice of a longer predictor output, no copy), h likewise (the target sequence shifted by
+ * one frame). D % 4 == 0, D <= 2048, strides multiples of 4 floats, pointers 16-byte aligned (stats 8-byte). One
+ * wave per row; every sum is a fixed tree, two runs are bitwise equal.
+ *
+ * vj_ac_loss_fwd: normalize != 0: zn = F.layer_norm(z, (D,)) without affine (biased variance, eps; vj_plan_frame's
+ * arithmetic, a zero-variance row gives zeros) and stats[b * R + r] = (mean, rstd); else zn = z exactly and stats
+ * is not touched. zn != NULL: zn -> dense [B][R][D]. rowsum != NULL: rowsum[b * R + r] = sum_d |zn - h| ** p (needs
+ * h; p == 1 and p == 2 without powf). rowsum == NULL: h is not read (a normalise-only call). */
+int vj_ac_loss_fwd(int B, int R, int D, const float* z, long z_sample_stride, long z_row_stride, const float* h,
+                   long h_sample_stride, long h_row_stride, int normalize, float eps, float p, float* zn,
+                   float* stats, float* rowsum, void* stream);
+/* g = s * sign(zn - h) * |zn - h| ** (p - 1) + gzn with s = scale * (gscale ? *gscale : 1) (gscale: a device
+ * scalar, e.g. the upstream gradient of the loss), sign(0) = 0; h == NULL: g = gzn; gzn (dense [B][R][D]) ==
+ * NULL reads as zero. zn is recomputed from z and the forward's stats (the same bits), not re-read. normalize
+ * != 0: dz = rstd * (g - mean(g) - zn * mean(g * zn)), else dz = g. dz dense [B][R][D], aliasing no input. */
+int vj_ac_loss_bwd(int B, int R, int D, const float* z, long z_sample_stride, long z_row_stride, const float* stats,
+                   const float* h, long h_sample_stride, long h_row_stride, int normalize, float p, float scale,
+                   const float* gscale, const float* gzn, float* dz, void* stream);
+/* loss[0] = (float)(scale * sum of rowsum[0..n)) on the device: f64, thread t of one 1024-thread workgroup adds
+ * rows t, t + 1024, ..., then a fixed tree. The step's loss is scale = 1 / (B * R * D * p). */
+int vj_ac_loss_reduce(long n, const float* rowsum, double scale, float* loss, void* stream);
+
 /* fp32-operand parity mode (vj_f32.hip): the encoder forward with f32 operands throughout, to show
  * the bf16 path's distance from the fp32 reference is operand rounding only. Not on the training
  * path. vj_gemm_f32: C = A B^T + bias (+ resid), epi as vj_gemm_bf16 (F32 = 1, F32_RESID = 2,

@@ -91,6 +91,9 @@ SIGNATURES = {
     "vj_pose_step": [_I, _P, _L, _P, _L, _P, _L, _P],
     "vj_plan_frame": [_I, _I, _I, _P, _L, _L, _I, _F, _P, _L, _P, _P, _P],
     "vj_cem_update": [_I, _I, _I, _P, _P, _D, _D, _D, _D, _P, _P, _P, _P],
+    "vj_ac_loss_fwd": [_I, _I, _I, _P, _L, _L, _P, _L, _L, _I, _F, _F, _P, _P, _P, _P],
+    "vj_ac_loss_bwd": [_I, _I, _I, _P, _L, _L, _P, _P, _L, _L, _I, _F, _F, _P, _P, _P, _P],
+    "vj_ac_loss_reduce": [_L, _P, _D, _P, _P],
 }
 
 _lib = None

@@ -973,3 +973,39 @@ def cross_attention(q, kv, B, nq, N, H, hd, scale):
     if torch.is_grad_enabled() and (q.requires_grad or kv.requires_grad):
         return _XAttnFn.apply(q, kv, B, nq, N, H, hd, scale)
     return ops.xattn_fwd(q, kv, B, nq, N, H, hd, scale)[0]
+
+
+# ------------------------------------------------------------------------------------------------
+# V-JEPA 2-AC post-training loss (app/vjepa_droid/train.py forward_predictions / loss_fn)
+
+
+class ACLossFn(torch.autograd.Function):
+    """(loss, zn) = ACLossFn.apply(z, h_view, normalize, loss_exp, eps[, want_zn]): zn = F.layer_norm(z, (D,))
+    (normalize) or z, loss = mean(|zn - h_view| ** loss_exp) / loss_exp as a 0-dim device tensor. want_zn False
+    (a loss-only call): zn is not written and comes back as None. z and h_view are f32
+    [B, R, D] views (a frame slice of a predictor output, the targets shifted by one frame); h_view None is the
+    normalise-only call of the roll-out (loss is None). The backward takes (dloss, dzn), either may be None: dzn
+    is what flows back from a later predictor pass that was fed zn."""
+
+    @staticmethod
+    def forward(ctx, z, h, normalize, loss_exp, eps, want_zn=True):
+        loss, zn, stats = ops.ac_loss_fwd(z, h, normalize=normalize, loss_exp=loss_exp, eps=eps, want_zn=want_zn)
+        ctx.save_for_backward(z, h, stats)
+        ctx.cfg = (bool(normalize), float(loss_exp))
+        ctx.set_materialize_grads(False)  # an unused output's gradient arrives as None, not as a zero tensor
+        if loss is None:
+            return None, zn
+        return loss.reshape(()), zn
+
+    @staticmethod
+    def backward(ctx, dloss, dzn):
+        z, h, stats = ctx.saved_tensors
+        normalize, loss_exp = ctx.cfg
+        if dloss is None:
+            h = None
+        if h is None and dzn is None:
+            return torch.zeros_like(z), None, None, None, None, None
+        gs = None if h is None else dloss.to(F32).reshape(1)
+        dz = ops.ac_loss_bwd(z, stats, h, normalize=normalize, loss_exp=loss_exp, scale=1.0 / z.numel(), gscale=gs,
+                             gzn=None if dzn is None else dzn.contiguous())
+        return dz, None, None, None, None, None

@@ -1051,6 +1051,96 @@ def cem_update(energy, actions, k, mean, std, momentum_mean=0.25, momentum_std=0
     return elite_idx
 
 
+# ------------------------------------------------------------------------------------------------
+# V-JEPA 2-AC post-training loss (vj_acloss.hip; app/vjepa_droid/train.py forward_predictions / loss_fn)
+def _rows3(t, name):
+    """f32 [B, R, D] view with unit column stride -> (sample stride, row stride); a size-1 dimension's stride is
+    arbitrary, so it is replaced by the dense one."""
+    if t.dtype != F32 or t.dim() != 3 or t.stride(2) != 1:
+        raise ValueError(f"{name}: expected an f32 [B, R, D] view with stride(2) == 1, got {t.dtype} "
+                         f"{tuple(t.shape)} {t.stride()}")
+    B, R, D = t.shape
+    rs = t.stride(1) if R > 1 else D
+    ss = t.stride(0) if B > 1 else (R - 1) * rs + D
+    return ss, rs
+
+
+def ac_loss_fwd(z, h=None, normalize=True, loss_exp=1.0, eps=1e-5, want_zn=True, zn=None, stats=None, rowsum=None,
+                loss=None):
+    """One predictor pass's loss side (vj_ac_loss_fwd + vj_ac_loss_reduce): zn = F.layer_norm(z, (D,)) (or z),
+    and mean(|zn - h| ** loss_exp) / loss_exp as a device scalar.
+
+    z, h f32 [B, R, D] views with stride(2) == 1 (a frame slice of a longer sequence, the targets shifted by a
+    frame: no copy is made). h None: a normalise-only call (no loss). Returns (loss f32 [1] or None, zn dense
+    [B, R, D] or None, stats f32 [B * R, 2] or None: per-row (mean, rstd), what ac_loss_bwd needs)."""
+    _dev(z, h, zn, stats, rowsum, loss)
+    zss, zrs = _rows3(z, "ac_loss_fwd: z")
+    B, R, D = z.shape
+    hss = hrs = 0
+    if h is not None:
+        if tuple(h.shape) != (B, R, D):
+            raise ValueError(f"ac_loss_fwd: h {tuple(h.shape)} does not match z {(B, R, D)}")
+        hss, hrs = _rows3(h, "ac_loss_fwd: h")
+        if rowsum is None:
+            rowsum = torch.empty(B * R, dtype=F32, device=z.device)
+        _f32_contig(rowsum, (B * R,), "ac_loss_fwd: rowsum")
+        if loss is None:
+            loss = torch.empty(1, dtype=F32, device=z.device)
+        _f32_contig(loss, (1,), "ac_loss_fwd: loss")
+    else:
+        rowsum = loss = None
+    if want_zn or zn is not None:
+        if zn is None:
+            zn = torch.empty(B, R, D, dtype=F32, device=z.device)
+        _f32_contig(zn, (B, R, D), "ac_loss_fwd: zn")
+    if normalize:
+        if stats is None:
+            stats = torch.empty(B * R, 2, dtype=F32, device=z.device)
+        _f32_contig(stats, (B * R, 2), "ac_loss_fwd: stats")
+    else:
+        stats = None
+    if zn is None and rowsum is None:
+        raise ValueError("ac_loss_fwd: nothing to do (no h and no zn wanted)")
+    _call("vj_ac_loss_fwd", B, R, D, _p(z), zss, zrs, _p(h), hss, hrs, int(bool(normalize)), float(eps),
+          float(loss_exp), _p(zn), _p(stats), _p(rowsum), _stream())
+    if rowsum is not None:
+        _call("vj_ac_loss_reduce", B * R, _p(rowsum), 1.0 / (float(B) * R * D * float(loss_exp)), _p(loss), _stream())
+    return loss, zn, stats
+
+
+def ac_loss_bwd(z, stats, h=None, normalize=True, loss_exp=1.0, scale=1.0, gscale=None, gzn=None, dz=None):
+    """Gradient of ac_loss_fwd with respect to z (vj_ac_loss_bwd): g = s sign(zn - h) |zn - h| ** (loss_exp - 1)
+    + gzn, s = scale * gscale[0] (gscale: a device scalar, e.g. the loss's upstream gradient; None: 1), then the
+    LayerNorm backward of g (normalize) or g itself. For the gradient of the mean loss, scale = 1 / (B R D).
+    h None: only gzn flows (a normalise-only forward). Returns dz, dense f32 [B, R, D]."""
+    _dev(z, stats, h, gscale, gzn, dz)
+    zss, zrs = _rows3(z, "ac_loss_bwd: z")
+    B, R, D = z.shape
+    hss = hrs = 0
+    if h is not None:
+        if tuple(h.shape) != (B, R, D):
+            raise ValueError(f"ac_loss_bwd: h {tuple(h.shape)} does not match z {(B, R, D)}")
+        hss, hrs = _rows3(h, "ac_loss_bwd: h")
+    if normalize:
+        if stats is None:
+            raise ValueError("ac_loss_bwd: normalize needs the forward's stats")
+        _f32_contig(stats, (B * R, 2), "ac_loss_bwd: stats")
+    else:
+        stats = None
+    if gzn is not None:
+        _f32_contig(gzn, (B, R, D), "ac_loss_bwd: gzn")
+    if gscale is not None and (gscale.dtype != F32 or gscale.numel() != 1):
+        raise ValueError(f"ac_loss_bwd: gscale must be one f32 value, got {gscale.dtype} {tuple(gscale.shape)}")
+    if h is None and gzn is None:
+        raise ValueError("ac_loss_bwd: nothing to do (neither h nor gzn)")
+    if dz is None:
+        dz = torch.empty(B, R, D, dtype=F32, device=z.device)
+    _f32_contig(dz, (B, R, D), "ac_loss_bwd: dz")
+    _call("vj_ac_loss_bwd", B, R, D, _p(z), zss, zrs, _p(stats), _p(h), hss, hrs, int(bool(normalize)),
+          float(loss_exp), float(scale), _p(gscale), _p(gzn), _p(dz), _stream())
+    return dz
+
+
 def check_finite(g, found_inf):
     _dev(g, found_inf)
     _call("vj_check_finite", g.numel(), _p(g), _p(found_inf), _stream())
