@@ -76,7 +76,7 @@ def test_wrapper_against_reference(num_steps):
 # ------------------------------------------------------------------------------------------------ trainer
 def _trainer(use_bfloat16=True, use_focal_loss=True, classifiers=None, n=3):
     from vjepa2_amd.evals.action_anticipation_frozen import AnticipationTrainer
-    from vjepa2_amd.evals.video_classification_frozen import init_opt
+    from vjepa2_amd.evals.probe import init_opt
 
     p = af.load()["probe"]
     cfg = p["cfg"]

@@ -93,13 +93,13 @@ def test_image_eval_main_end_to_end(tmp_path, monkeypatch):
                                         dict(lr=3e-3, start_lr=3e-3, final_lr=0.0, weight_decay=0.2,
                                              final_weight_decay=0.2, warmup=0.0)])))
 
-    save = vcf.save_checkpoint
+    save = app.save_checkpoint
 
     def save_and_keep(path, classifiers, optimizers, scalers, epoch, batch_size, world_size):
         save(path, classifiers, optimizers, scalers, epoch, batch_size, world_size)
         shutil.copy(path, f"{path}.e{epoch}")
 
-    monkeypatch.setattr(vcf, "save_checkpoint", save_and_keep)
+    monkeypatch.setattr(app, "save_checkpoint", save_and_keep)
     sched = []
     step = vcf.ProbeTrainer.train_step
 

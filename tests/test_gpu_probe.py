@@ -44,7 +44,8 @@ def _flat(sd):
 
 
 def _trainer(use_bfloat16=True):
-    from vjepa2_amd.evals.video_classification_frozen import ProbeTrainer, init_opt
+    from vjepa2_amd.evals.probe import init_opt
+    from vjepa2_amd.evals.video_classification_frozen import ProbeTrainer
 
     d = pf.load()
     cfg = d["cfg"]
@@ -166,7 +167,7 @@ def test_probe_schedule_and_top1(run):
 def test_probe_optimizer_state_interchange(run):
     """Each head's state_dict() loads into a torch.optim.AdamW built as eval.py:471-483 builds it; the
     reference optimizer's recorded state loads into ours."""
-    from vjepa2_amd.evals.video_classification_frozen import load_opt_state
+    from vjepa2_amd.evals.probe import load_opt_state
 
     d = pf.load()
     tr = run["trainer"]

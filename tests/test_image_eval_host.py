@@ -75,10 +75,15 @@ def test_checkpoint_keys_round_trip(tmp_path):
     """latest.pt through the shared save_checkpoint / load_checkpoint: the reference's keys
     (eval.py:209-216), 'module.'-prefixed classifier keys, optimizer state and mc_* group keys restored,
     val_only restoring the classifiers alone."""
+    from vjepa2_amd.evals import action_anticipation_frozen as aaf
     from vjepa2_amd.evals import image_classification_frozen as app
+    from vjepa2_amd.evals import probe
     from vjepa2_amd.evals import video_classification_frozen as vcf
 
-    assert app.vcf is vcf and app.ProbeTrainer is vcf.ProbeTrainer and app.init_opt is vcf.init_opt  # shared, not copied
+    assert app.ProbeTrainer is vcf.ProbeTrainer  # shared, not copied
+    for mod in (app, vcf, aaf):
+        assert mod.init_opt is probe.init_opt and mod.save_checkpoint is probe.save_checkpoint
+        assert mod.load_checkpoint is probe.load_checkpoint
 
     def heads(seed):
         torch.manual_seed(seed)
@@ -94,7 +99,7 @@ def test_checkpoint_keys_round_trip(tmp_path):
         c(torch.randn(5, 4)).sum().backward()
         o.step()
     path = tmp_path / "latest.pt"
-    vcf.save_checkpoint(path, cs, os_, [None, None], 3, 16, 1)
+    probe.save_checkpoint(path, cs, os_, [None, None], 3, 16, 1)
     ck = torch.load(path, weights_only=True)
     assert set(ck) == {"classifiers", "opt", "scaler", "epoch", "batch_size", "world_size"}
     assert ck["epoch"] == 3 and ck["batch_size"] == 16 and ck["world_size"] == 1 and ck["scaler"] is None
@@ -102,14 +107,14 @@ def test_checkpoint_keys_round_trip(tmp_path):
     cs2, os2 = heads(2)
     for o in os2:
         o.param_groups[0]["mc_ref_lr"] = 7.0
-    *_, epoch = vcf.load_checkpoint(path, cs2, os2, [None, None])
+    *_, epoch = probe.load_checkpoint(path, cs2, os2, [None, None])
     assert epoch == 3
     assert all(torch.equal(a.weight, b.weight) for a, b in zip(cs, cs2))
     assert os2[0].param_groups[0]["mc_ref_lr"] == 1e-3 and os2[1].param_groups[0]["mc_final_wd"] == 0.4
     assert all(torch.equal(os_[0].state_dict()["state"][k]["exp_avg"], v["exp_avg"])
                for k, v in os2[0].state_dict()["state"].items())
     cs3, os3 = heads(3)
-    *_, epoch = vcf.load_checkpoint(path, cs3, os3, [None, None], val_only=True)
+    *_, epoch = probe.load_checkpoint(path, cs3, os3, [None, None], val_only=True)
     assert epoch == 0 and torch.equal(cs3[1].bias, cs[1].bias) and os3[0].state_dict()["state"] == {}
 
 

@@ -24,7 +24,7 @@ def _group(kw, ipe):
 def test_schedulers_reproduce_reference_sequence():
     """WarmupCosineLRSchedule / CosineWDSchedule (eval.py:490-537) give the fixture's LR and WD of every
     iteration, float for float."""
-    from vjepa2_amd.evals.video_classification_frozen import CosineWDSchedule, WarmupCosineLRSchedule
+    from vjepa2_amd.evals.probe import CosineWDSchedule, WarmupCosineLRSchedule
 
     d = pf.load()
     cfg = d["cfg"]
@@ -82,7 +82,7 @@ def test_synthetic_dataset_tuple_layout():
 
 def test_top_one_meter_matches_average_meter():
     """TopOneMeter: the unweighted mean of per-iteration float32 percentages (eval.py:328-331)."""
-    from vjepa2_amd.evals.video_classification_frozen import TopOneMeter
+    from vjepa2_amd.evals.probe import TopOneMeter
 
     m = TopOneMeter(2)
     m.update(torch.tensor([1, 3], dtype=torch.int32), 3)

@@ -25,7 +25,8 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 from vjepa2_amd import ops  # noqa: E402
 from vjepa2_amd.attentive_pooler import AttentiveClassifier  # noqa: E402
-from vjepa2_amd.evals.video_classification_frozen import ProbeTrainer, init_opt  # noqa: E402
+from vjepa2_amd.evals.probe import init_opt  # noqa: E402
+from vjepa2_amd.evals.video_classification_frozen import ProbeTrainer  # noqa: E402
 
 
 def _sync_time(fn):

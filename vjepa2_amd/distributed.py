@@ -51,6 +51,20 @@ def init_distributed(port=37129, rank_and_world_size=(None, None), backend=None)
     return world, rank
 
 
+def env_world_size():
+    """The world size a launcher asked for (init_distributed's sources), without joining a process
+    group: the larger of an initialised group's and the environment's."""
+    env = os.environ
+    world = 1
+    if dist.is_available() and dist.is_initialized():
+        world = dist.get_world_size()
+    if "RANK" in env and "WORLD_SIZE" in env:
+        world = max(world, int(env["WORLD_SIZE"]))
+    elif "SLURM_NTASKS" in env:
+        world = max(world, int(env["SLURM_NTASKS"]))
+    return world
+
+
 class _Bucket:
     __slots__ = ("view", "pending", "params", "work")
 

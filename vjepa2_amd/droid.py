@@ -40,6 +40,7 @@ from . import ops
 from . import vision_transformer as video_vit
 from .ac_predictor import vit_ac_predictor
 from .arena import FlatArena, FusedAdamW, readiness_order, wd_split
+from .distributed import env_world_size
 from .functions import ACLossFn, join_wgrad_stream, refresh_weight_transposes
 from .planning import poses_to_diff
 from .schedulers import CosineWDSchedule, WSDSchedule
@@ -372,12 +373,10 @@ def settings(args):
 def main(args, resume_preempt=False):
     """app/vjepa_droid/train.py:54-524 on ACTrainer. Returns the per-iteration losses. resume_preempt is accepted
     and unused, as in the reference's main (train.py:54, 294): the run resumes whenever latest.pt exists."""
-    from .evals.video_classification_frozen import _env_world_size
-
     c = settings(args)
     # the app's own refusals before anything is put on the device; nothing is written before the models are built
     # (a predictor variant that VisionTransformerPredictorAC refuses raises from init_video_model)
-    world_size, rank = _env_world_size(), 0
+    world_size, rank = env_world_size(), 0
     if world_size > 1:
         raise NotImplementedError(f"V-JEPA 2-AC post-training on the HIP path runs on one GPU (world size "
                                   f"{world_size} requested): the predictor's gradient all-reduce is not wired")

@@ -29,8 +29,9 @@ must be below it: AnticipativeWrapper computes the anticipation steps on the hos
 loader as a CPU tensor) and raises ValueError before any launch otherwise. The EK100 configs are inside the
 range (predictor num_frames 64, clips of 32 frames).
 
-Precision: optimization.use_bfloat16 has the merged probe's meaning (video_classification_frozen): bf16 GEMM
-operands, loss scale 1, a per-classifier device-side skip when a gradient holds an inf or NaN.
+Precision: optimization.use_bfloat16 has the meaning it has for every probe here (evals/probe.py, which also
+holds what this eval shares with the video and image evals): bf16 GEMM operands, loss scale 1, a
+per-classifier device-side skip when a gradient holds an inf or NaN.
 Multi-GPU probe training (world size > 1), real EK100 decoding and the COIN annotations are not implemented:
 the data is a synthetic stand-in with the loader's sample layout (video, verb, noun, anticipation time).
 """
@@ -48,11 +49,13 @@ from .. import ops
 from .. import predictor as vit_pred
 from .. import vision_transformer as vit
 from ..attentive_pooler import AttentivePooler
-from ..functions import join_wgrad_stream, refresh_weight_transposes
-from .video_classification_frozen import _env_world_size, _strip, init_opt, load_opt_state
+from ..distributed import env_world_size
+from . import probe
+from .probe import load_checkpoint  # noqa: F401  (resume() calls it; here as save_checkpoint's counterpart)
+from .probe import (FrozenProbeTrainer, checked_labels, frozen, init_device, init_opt, load_pretrained, output_paths,
+                    resume, save_checkpoint)
 
 logger = logging.getLogger(__name__)
-_GLOBAL_SEED = 0
 ANTICIPATION_MODULE = "evals.action_anticipation_frozen.modelcustom.vit_encoder_predictor_concat_ar"
 HEADS = ("verb", "noun", "action")
 
@@ -117,18 +120,6 @@ class AnticipativeWrapper(nn.Module):
         return torch.cat(acc, dim=1)
 
 
-def _load_pretrained(model, pretrained, what):
-    pretrained = _strip(pretrained)
-    for k, v in model.state_dict().items():
-        if k not in pretrained:
-            logger.info('key "%s" could not be found in loaded state dict', k)
-        elif pretrained[k].shape != v.shape:
-            logger.info('key "%s" is of different shape in model and loaded state dict', k)
-            pretrained[k] = v
-    msg = model.load_state_dict(pretrained, strict=False)
-    logger.info("loaded pretrained %s with msg: %s", what, msg)
-
-
 def init_module(module_name, device, frames_per_clip, frames_per_second, resolution, checkpoint, model_kwargs,
                 wrapper_kwargs):
     """models.py:71-110 + modelcustom/vit_encoder_predictor_concat_ar.py:37-116: the HIP encoder and predictor
@@ -140,21 +131,18 @@ def init_module(module_name, device, frames_per_clip, frames_per_second, resolut
     ck = torch.load(checkpoint, map_location="cpu", weights_only=True)
     enc_kwargs = dict(model_kwargs["encoder"])
     encoder = vit.__dict__[enc_kwargs.get("model_name")](img_size=resolution, num_frames=frames_per_clip, **enc_kwargs)
-    _load_pretrained(encoder, ck[enc_kwargs.get("checkpoint_key")], "model")
+    load_pretrained(encoder, ck[enc_kwargs.get("checkpoint_key")], "model")
     prd_kwargs = dict(model_kwargs["predictor"])
     predictor = vit_pred.__dict__[prd_kwargs.get("model_name")](
         img_size=resolution, embed_dim=encoder.embed_dim, patch_size=encoder.patch_size,
         tubelet_size=encoder.tubelet_size, **prd_kwargs)
-    _load_pretrained(predictor, ck[prd_kwargs.get("checkpoint_key")], "predictor")
+    load_pretrained(predictor, ck[prd_kwargs.get("checkpoint_key")], "predictor")
     del ck
     model = AnticipativeWrapper(encoder=encoder, predictor=predictor, frames_per_second=frames_per_second,
                                 crop_size=resolution, patch_size=encoder.patch_size, tubelet_size=encoder.tubelet_size,
                                 **(wrapper_kwargs or {}))
     model.embed_dim = encoder.embed_dim
-    model = model.to(device).eval()
-    for p in model.parameters():
-        p.requires_grad = False
-    return model
+    return frozen(model, device)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -254,29 +242,20 @@ def read_annotation_pairs(path):
 
 
 # ------------------------------------------------------------------------------------------------
-class AnticipationTrainer:
+class AnticipationTrainer(FrozenProbeTrainer):
     """The anticipation probe step (eval.py:470-535, 622-665) over arena-owned classifiers, one by one."""
 
     def __init__(self, model, classifiers, optimizers, scalers=None, schedulers=None, wd_schedulers=None,
                  use_bfloat16=False, use_focal_loss=True, alpha=0.25, gamma=2.0, k=5):
+        super().__init__(classifiers, optimizers, scalers, schedulers, wd_schedulers, use_bfloat16)
         self.model = model
-        self.classifiers = list(classifiers)
-        self.opts = list(optimizers)
-        self.scalers = list(scalers) if scalers is not None else [None] * len(self.opts)
-        self.schedulers = list(schedulers) if schedulers is not None else []
-        self.wd_schedulers = list(wd_schedulers) if wd_schedulers is not None else []
-        self.use_bfloat16 = bool(use_bfloat16)
         self.use_focal_loss = bool(use_focal_loss)
         self.alpha, self.gamma, self.k = alpha, gamma, k  # sigmoid_focal_loss's defaults, ClassMeanRecall's k
         self.heads = self.classifiers[0].heads
         self.metrics = {True: None, False: None}  # training / validation: {head: [ClassMeanRecall per classifier]}
-        # the last step's values, for logging and tests: LR / WD as applied, losses [classifiers, heads]
-        # (device), hit flags [classifiers, heads, B] (device)
-        self.last_lr, self.last_wd, self.last_losses, self.last_hits = [], [], None, None
-        # debug hooks (tests): on_logits(i, dict) after classifier i's forward, on_grads(i) when its gradients
-        # are complete and before its update
-        self.on_logits = None
-        self.on_grads = None
+        # the last step's losses [classifiers, heads] (device) and hit flags [classifiers, heads, B] (device);
+        # on_logits is given the classifier's dict of logits
+        self.last_losses, self.last_hits = None, None
 
     def _linear(self, c, head):
         return getattr(c, f"{head}_classifier")
@@ -295,30 +274,10 @@ class AnticipationTrainer:
             out[h] = dict(accuracy=max(r["accuracy"] for r in rs), recall=max(r["recall"] for r in rs))
         return out
 
-    def _labels(self, labels, device):
-        out = []
-        for h in self.heads:
-            lb = labels[h]
-            C = self._linear(self.classifiers[0], h).out_features
-            if not lb.is_cuda:  # loaders deliver CPU labels: validated here, once for every classifier
-                lo, hi = int(lb.min()), int(lb.max())
-                if lo < 0 or hi >= C:
-                    raise IndexError(f"{h} label {hi if hi >= C else lo} out of range for {C} classes")
-                lb = lb.to(device, non_blocking=True)
-            out.append(lb)
-        return out
-
     def train_step(self, clips, anticipation_times, labels):
         """One training iteration (eval.py:479-535). labels: {head: [B] unified class ids}. Returns the
         losses [classifiers, heads] (device); a classifier's loss is their sum."""
-        for s in self.schedulers:
-            s.step()
-        for s in self.wd_schedulers:
-            s.step()
-        self.last_lr = [o.param_groups[0]["lr"] for o in self.opts]
-        self.last_wd = [o.param_groups[0]["weight_decay"] for o in self.opts]
-        for c in self.classifiers:
-            c.train(True)
+        self._begin(True)
         with torch.no_grad():
             x = self.model(clips, anticipation_times).detach()
         return self._classifiers(x, labels, None, training=True)
@@ -326,8 +285,7 @@ class AnticipationTrainer:
     def validate(self, clips, anticipation_times, labels, valid=None):
         """One validation iteration (eval.py:629-665). valid: {head: bool / uint8 device mask [C] of the classes
         that count for the ranking} or None."""
-        for c in self.classifiers:
-            c.train(False)
+        self._begin(False)
         with torch.no_grad():
             x = self.model(clips, anticipation_times).detach()
             return self._classifiers(x, labels, valid, training=False)
@@ -337,7 +295,8 @@ class AnticipationTrainer:
             self.reset_metrics(training)
         heads, n, dev = self.heads, len(self.heads), x.device
         B = x.shape[0]
-        labels = self._labels(labels, dev)
+        labels = [checked_labels(labels[h], self._linear(self.classifiers[0], h).out_features, dev, what=h)
+                  for h in heads]
         masks = None if valid is None else [valid.get(h) for h in heads]
         losses = torch.empty(len(self.classifiers), n, dtype=torch.float32, device=dev)
         hits = torch.empty(len(self.classifiers), n, B, dtype=torch.int32, device=dev)
@@ -362,24 +321,11 @@ class AnticipationTrainer:
                 ops.focal(logits, labels, tp, fn_, valid=masks, k=self.k, loss_kind=0, out=(None, None, None, hits[i]))
             if training:
                 torch.autograd.backward(logits, dls)
-                join_wgrad_stream()
-                for a in opt.arenas:
-                    a.finalize_grads()
-                if self.on_grads is not None:
-                    self.on_grads(i)
-                found = opt.check_finite() if self.use_bfloat16 else None
-                opt.step(found_inf=found)
-                opt.zero_grad()
+                self._update(i, opt)
             del out, logits, dls  # this classifier's activations go before the next one's are made
-        if training:
-            refresh_weight_transposes()  # the next backward's W^T operands, one launch
+        self._end(training)
         self.last_losses, self.last_hits = losses, hits
         return losses
-
-    def sync_bf16(self):
-        for o in self.opts:
-            for a in o.arenas:
-                a.sync_bf16()
 
 
 # ------------------------------------------------------------------------------------------------
@@ -417,34 +363,6 @@ def make_dataloader(pairs, batch_size, frames_per_clip, crop_size, anticipation_
     ds = SyntheticAnticipationDataset(pairs, frames_per_clip, crop_size, anticipation_time_sec, seed_offset=seed_offset)
     return torch.utils.data.DataLoader(ds, batch_size=batch_size, shuffle=False, num_workers=num_workers,
                                        drop_last=True, persistent_workers=num_workers > 0)
-
-
-def save_checkpoint(path, classifiers, optimizers, scalers, epoch, batch_size, world_size):
-    """eval.py:306-316: the reference's keys; classifier keys with DistributedDataParallel's prefix."""
-    torch.save({"classifiers": [{"module." + k: v.detach().cpu().clone() for k, v in c.state_dict().items()}
-                                for c in classifiers],
-                "opt": [o.state_dict() for o in optimizers],
-                "scaler": None if scalers[0] is None else [s.state_dict() for s in scalers],
-                "epoch": epoch, "batch_size": batch_size, "world_size": world_size}, path)
-
-
-def load_checkpoint(r_path, classifiers, opt, scaler, val_only=False):
-    """utils / eval.py load_checkpoint (tensor-only checkpoint: weights_only=True); classifier keys with or
-    without the 'module.' prefix."""
-    ck = torch.load(r_path, map_location="cpu", weights_only=True)
-    for c, sd in zip(classifiers, ck["classifiers"]):
-        c.load_state_dict({(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()})
-    for o in opt:
-        for a in o.arenas:
-            a.sync_bf16()
-    if val_only:
-        return classifiers, opt, scaler, 0
-    for o, sd in zip(opt, ck["opt"]):
-        load_opt_state(o, sd)
-    if scaler is not None and scaler[0] is not None and ck.get("scaler") is not None:
-        for s, sd in zip(scaler, ck["scaler"]):
-            s.load_state_dict(sd)
-    return classifiers, opt, scaler, ck["epoch"]
 
 
 def _class_mask(ids, num_classes, device):
@@ -490,71 +408,47 @@ def _csv_row(epoch, train, val, verb_noun):
     return [str(epoch)] + ["%.5f" % v for v in vals]
 
 
+def read_config(args_eval, resume_preempt=False):
+    """The reference's keys (eval.py:52-126); data: the section itself, for the synthetic dataset's four."""
+    c = probe.read_config(args_eval, resume_preempt)
+    args_data = args_eval.get("experiment").get("data")
+    c.update(data=args_data, dataset=args_data.get("dataset"),
+             num_workers=args_data.get("num_workers", 0),  # synthetic data: no decode to hide
+             frames_per_clip=args_data.get("frames_per_clip"), frames_per_second=args_data.get("frames_per_second"),
+             train_anticipation_time_sec=args_data.get("train_anticipation_time_sec"),
+             val_anticipation_time_sec=args_data.get("anticipation_time_sec"),
+             train_annotations_path=args_data.get("dataset_train"), val_annotations_path=args_data.get("dataset_val"),
+             use_focal_loss=args_eval.get("experiment").get("optimization").get("use_focal_loss", False))
+    return c
+
+
 def main(args_eval, resume_preempt=False):
     """eval.py:52-441. Returns the validation metrics {head: dict(accuracy, recall)} of the last epoch run."""
-    val_only = args_eval.get("val_only", False)
-    pretrain_folder = args_eval.get("folder", None)
-    resume_checkpoint = args_eval.get("resume_checkpoint", False) or resume_preempt
-    eval_tag = args_eval.get("tag", None)
+    c = read_config(args_eval, resume_preempt)
+    val_only, batch_size, num_epochs, use_bfloat16 = c["val_only"], c["batch_size"], c["num_epochs"], c["use_bfloat16"]
+    args_data = c["data"]
 
-    args_pretrain = args_eval.get("model_kwargs")
-    checkpoint = args_pretrain.get("checkpoint")
-    module_name = args_pretrain.get("module_name")
-    args_model = args_pretrain.get("pretrain_kwargs")
-    args_wrapper = args_pretrain.get("wrapper_kwargs")
-    args_exp = args_eval.get("experiment")
-    args_classifier = args_exp.get("classifier")
-    num_probe_blocks = args_classifier.get("num_probe_blocks", 1)
-    num_heads = args_classifier.get("num_heads")
-    args_data = args_exp.get("data")
-    dataset = args_data.get("dataset")
-    num_workers = args_data.get("num_workers", 0)  # synthetic data: no decode to hide
-    frames_per_clip = args_data.get("frames_per_clip")
-    frames_per_second = args_data.get("frames_per_second")
-    resolution = args_data.get("resolution", 224)
-    train_anticipation_time_sec = args_data.get("train_anticipation_time_sec")
-    val_anticipation_time_sec = args_data.get("anticipation_time_sec")
-    train_annotations_path = args_data.get("dataset_train")
-    val_annotations_path = args_data.get("dataset_val")
-    args_opt = args_exp.get("optimization")
-    batch_size = args_opt.get("batch_size")
-    num_epochs = args_opt.get("num_epochs")
-    use_bfloat16 = args_opt.get("use_bfloat16")
-    use_focal_loss = args_opt.get("use_focal_loss", False)
-    opt_kwargs = [dict(ref_wd=kw.get("weight_decay"), final_wd=kw.get("final_weight_decay"),
-                       start_lr=kw.get("start_lr"), ref_lr=kw.get("lr"), final_lr=kw.get("final_lr"),
-                       warmup=kw.get("warmup")) for kw in args_opt.get("multihead_kwargs")]
-
-    world_size, rank = _env_world_size(), 0
+    world_size, rank = env_world_size(), 0
     if world_size > 1:
         raise NotImplementedError(f"action_anticipation_frozen on the HIP path runs on one GPU (world size "
                                   f"{world_size} requested): the classifiers' gradient all-reduce and the TP / FN "
                                   "all-reduce (metrics.py:47-48) are not wired")
-    if module_name != ANTICIPATION_MODULE:
-        raise NotImplementedError(f"model module {module_name!r}: only {ANTICIPATION_MODULE} is ported")
-    if dataset in ["COIN_anticipation"]:
+    if c["module_name"] != ANTICIPATION_MODULE:
+        raise NotImplementedError(f"model module {c['module_name']!r}: only {ANTICIPATION_MODULE} is ported")
+    if c["dataset"] in ["COIN_anticipation"]:
         raise NotImplementedError("the COIN anticipation annotations (action-only labels) are not ported")
-    if not torch.cuda.is_available():
-        raise RuntimeError("the anticipation probe on the HIP path needs an MI355X (no CPU path)")
-    device = torch.device("cuda", 0)
-    torch.cuda.set_device(device)
-    np.random.seed(_GLOBAL_SEED)
-    torch.manual_seed(_GLOBAL_SEED)
-
-    folder = os.path.join(pretrain_folder, "action_anticipation_frozen/")
-    if eval_tag is not None:
-        folder = os.path.join(folder, eval_tag)
+    device = init_device("the anticipation probe")
+    folder, log_file, latest_path = output_paths(c["pretrain_folder"], "action_anticipation_frozen", c["eval_tag"],
+                                                 rank)
     os.makedirs(folder, exist_ok=True)
-    log_file = os.path.join(folder, f"log_r{rank}.csv")
-    latest_path = os.path.join(folder, "latest.pt")
     with open(log_file, "a", newline="") as f:  # CSVLogger prints its header when it is made (logging.py:51-57)
         csv.writer(f).writerow(CSV_COLUMNS)
 
     # annotations: (verb, noun) pairs from the CSVs when both exist, else synthetic ones
-    if train_annotations_path and val_annotations_path and os.path.exists(train_annotations_path) \
-            and os.path.exists(val_annotations_path):
-        train_pairs = read_annotation_pairs(train_annotations_path)
-        val_pairs = read_annotation_pairs(val_annotations_path)
+    train_path, val_path = c["train_annotations_path"], c["val_annotations_path"]
+    if train_path and val_path and os.path.exists(train_path) and os.path.exists(val_path):
+        train_pairs = read_annotation_pairs(train_path)
+        val_pairs = read_annotation_pairs(val_path)
     else:
         n_train = int(args_data.get("num_samples", 64 * batch_size))
         n_val = int(args_data.get("num_val_samples", n_train))
@@ -565,35 +459,34 @@ def main(args_eval, resume_preempt=False):
     val_pairs = [p for p, k in zip(val_pairs, classes["val_keep"]) if k]
     verb_classes, noun_classes, action_classes = classes["verbs"], classes["nouns"], classes["actions"]
 
-    model = init_module(module_name=module_name, frames_per_clip=frames_per_clip, frames_per_second=frames_per_second,
-                        resolution=resolution, checkpoint=checkpoint, model_kwargs=args_model,
-                        wrapper_kwargs=args_wrapper, device=device)
-    classifiers = init_classifier(embed_dim=model.embed_dim, num_heads=num_heads, verb_classes=verb_classes,
+    model = init_module(module_name=c["module_name"], frames_per_clip=c["frames_per_clip"],
+                        frames_per_second=c["frames_per_second"], resolution=c["resolution"],
+                        checkpoint=c["checkpoint"], model_kwargs=c["args_model"], wrapper_kwargs=c["args_wrapper"],
+                        device=device)
+    classifiers = init_classifier(embed_dim=model.embed_dim, num_heads=c["num_heads"], verb_classes=verb_classes,
                                   noun_classes=noun_classes, action_classes=action_classes,
-                                  num_blocks=num_probe_blocks, device=device, num_classifiers=len(opt_kwargs))
-    kw = dict(batch_size=batch_size, frames_per_clip=frames_per_clip, crop_size=resolution, num_workers=num_workers)
-    train_loader = make_dataloader(train_pairs, anticipation_time_sec=train_anticipation_time_sec, **kw)
-    val_loader = make_dataloader(val_pairs, anticipation_time_sec=val_anticipation_time_sec, seed_offset=1 << 20, **kw)
+                                  num_blocks=c["num_probe_blocks"], device=device,
+                                  num_classifiers=len(c["opt_kwargs"]))
+    kw = dict(batch_size=batch_size, frames_per_clip=c["frames_per_clip"], crop_size=c["resolution"],
+              num_workers=c["num_workers"])
+    train_loader = make_dataloader(train_pairs, anticipation_time_sec=c["train_anticipation_time_sec"], **kw)
+    val_loader = make_dataloader(val_pairs, anticipation_time_sec=c["val_anticipation_time_sec"], seed_offset=1 << 20,
+                                 **kw)
     ipe = len(train_loader)
     logger.info("Dataloader created... iterations per epoch: %d (val %d)", ipe, len(val_loader))
 
-    optimizer, scaler, scheduler, wd_scheduler = init_opt(classifiers=classifiers, opt_kwargs=opt_kwargs,
+    optimizer, scaler, scheduler, wd_scheduler = init_opt(classifiers=classifiers, opt_kwargs=c["opt_kwargs"],
                                                           iterations_per_epoch=ipe, num_epochs=num_epochs,
                                                           use_bfloat16=use_bfloat16)
     trainer = AnticipationTrainer(model, classifiers, optimizer, scaler, scheduler, wd_scheduler,
-                                  use_bfloat16=use_bfloat16, use_focal_loss=use_focal_loss)
+                                  use_bfloat16=use_bfloat16, use_focal_loss=c["use_focal_loss"])
     valid = dict(verb=_class_mask(classes["val_verbs"], len(verb_classes), device),
                  noun=_class_mask(classes["val_nouns"], len(noun_classes), device),
                  action=_class_mask(classes["val_actions"], len(action_classes), device))
 
     start_epoch = 0
-    if resume_checkpoint and os.path.exists(latest_path):
-        *_, start_epoch = load_checkpoint(latest_path, classifiers, optimizer, scaler, val_only=val_only)
-        for _ in range(start_epoch * ipe):
-            [s.step() for s in scheduler]
-            [s.step() for s in wd_scheduler]
-        if val_only:
-            start_epoch = 0
+    if c["resume_checkpoint"] and os.path.exists(latest_path):
+        start_epoch = resume(latest_path, classifiers, optimizer, scaler, scheduler, wd_scheduler, ipe, val_only)
 
     val_metrics = None
     for epoch in range(start_epoch, num_epochs):

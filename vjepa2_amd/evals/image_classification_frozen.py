@@ -5,8 +5,9 @@ its modelcustom/vit_encoder.py:38-83 init_module): the IN1K configs of configs/e
 (eval.py:263-324): schedulers, the frozen encoder under no_grad on the image repeated along time, every
 attentive classifier, CrossEntropyLoss, top-1 as 100 * correct / len(imgs) into a per-head average,
 backward, one AdamW per classifier. That is the video probe's step with ONE view, so the step is
-video_classification_frozen.ProbeTrainer (vj_xent with views=1, the arena AdamW, the bf16 convention
-described there), and the schedules, init_opt, the meter and the checkpoint functions are that module's.
+video_classification_frozen.ProbeTrainer (vj_xent with views=1, the arena AdamW, the bf16 convention of
+evals/probe.py), and the schedules, init_opt, the meter, the checkpoint functions and the epoch loop are
+evals/probe.py's, as they are for the video eval.
 The encoder is the HIP VisionTransformer's forward(); the image repeat (eval: 0.2 GB at the IN1K shape,
 against an encoder pass hundreds of times that) is a stride-0 expand that the patch embed reads.
 Data is synthetic (timm, torchvision and an image folder are absent): data.num_samples /
@@ -18,16 +19,17 @@ import logging
 import math
 import os
 
-import numpy as np
 import torch
 
 from .. import vision_transformer as vit
 from ..attentive_pooler import AttentiveClassifier
-from . import video_classification_frozen as vcf
-from .video_classification_frozen import ProbeTrainer, init_opt
+from ..distributed import env_world_size
+from . import probe
+from .probe import load_checkpoint  # noqa: F401  (resume() calls it; here as save_checkpoint's counterpart)
+from .probe import frozen, init_device, init_opt, load_pretrained, resume, save_checkpoint
+from .video_classification_frozen import ProbeTrainer
 
 logger = logging.getLogger(__name__)
-_GLOBAL_SEED = 0
 IMAGE_MODULE = "evals.image_classification_frozen.modelcustom.vit_encoder"
 
 
@@ -73,20 +75,9 @@ def init_module(module_name, resolution, checkpoint, model_kwargs, wrapper_kwarg
     model = vit.__dict__[enc_kwargs.get("model_name")](input_size=resolution, num_frames=nframes, **enc_kwargs)
     logger.info("Loading pretrained model from %s", checkpoint)
     ck = torch.load(checkpoint, map_location="cpu", weights_only=True)
-    pretrained = vcf._strip(ck[ckp_key])
-    for k, v in model.state_dict().items():
-        if k not in pretrained:
-            logger.info('key "%s" could not be found in loaded state dict', k)
-        elif pretrained[k].shape != v.shape:
-            logger.info('key "%s" is of different shape in model and loaded state dict', k)
-            pretrained[k] = v
-    msg = model.load_state_dict(pretrained, strict=False)
-    logger.info("loaded pretrained model with msg: %s", msg)
+    load_pretrained(model, ck[ckp_key], "model")
     del ck
-    model = ImageAsVideoEncoder(model, nframes).to(device).eval()
-    for p in model.parameters():
-        p.requires_grad = False
-    return model
+    return frozen(ImageAsVideoEncoder(model, nframes), device)
 
 
 class SyntheticLabelledImageDataset(torch.utils.data.Dataset):
@@ -134,72 +125,42 @@ class CSVLog:
             print("%d,%.5f,%.5f" % (epoch, train_acc, val_acc), file=f)
 
 
+def _unpack(data, device):
+    """eval.py:287: the loader's (imgs, labels) as ProbeTrainer's (clips, clip_indices, labels)."""
+    return data[0].to(device, non_blocking=True), None, data[1]
+
+
 def run_one_epoch(trainer, device, training, data_loader, log_every=20):
-    """eval.py:263-324: returns the best head's running top-1 (%); read back from the device only when
-    it is logged and at the end."""
-    meter = trainer.train_meter if training else trainer.val_meter
-    meter.reset()
-    for itr, data in enumerate(data_loader):
-        imgs, labels = data[0].to(device, non_blocking=True), data[1]
-        if training:
-            trainer.train_step(imgs, None, labels)
-        else:
-            trainer.validate(imgs, None, labels)
-        if itr % log_every == 0:
-            agg = meter.avg()
-            logger.info("[%5d] %.3f%% [%.3f%% %.3f%%] [mem: %.2e]", itr, agg.max(), agg.mean(), agg.min(),
-                        torch.cuda.max_memory_allocated() / 1024.0**2)
-    return float(meter.avg().max())
+    """eval.py:263-324: returns the best head's running top-1 (%)."""
+    return probe.run_one_epoch(trainer, device, training, data_loader, _unpack, log_every)
 
 
 def read_config(args_eval, resume_preempt=False):
     """The reference's keys (eval.py:56-103) plus the synthetic dataset's two."""
-    args_pretrain = args_eval.get("model_kwargs")
-    args_exp = args_eval.get("experiment")
-    args_classifier = args_exp.get("classifier")
-    args_data = args_exp.get("data")
-    args_opt = args_exp.get("optimization")
-    return dict(
-        val_only=args_eval.get("val_only", False), pretrain_folder=args_eval.get("folder", None),
-        resume_checkpoint=args_eval.get("resume_checkpoint", False) or resume_preempt,
-        eval_tag=args_eval.get("tag", None), num_workers=args_eval.get("num_workers", 0),
-        checkpoint=args_pretrain.get("checkpoint"), module_name=args_pretrain.get("module_name"),
-        args_model=args_pretrain.get("pretrain_kwargs"), args_wrapper=args_pretrain.get("wrapper_kwargs"),
-        num_probe_blocks=args_classifier.get("num_probe_blocks", 1), num_heads=args_classifier.get("num_heads", 16),
-        dataset_name=args_data.get("dataset_name"), num_classes=args_data.get("num_classes"),
-        root_path=args_data.get("root_path", None), image_folder=args_data.get("image_folder", None),
-        resolution=args_data.get("resolution", 224), normalization=args_data.get("normalization", None),
-        num_samples=args_data.get("num_samples"), num_val_samples=args_data.get("num_val_samples"),
-        batch_size=args_opt.get("batch_size"), num_epochs=args_opt.get("num_epochs"),
-        use_bfloat16=args_opt.get("use_bfloat16"),
-        opt_kwargs=[dict(ref_wd=kw.get("weight_decay"), final_wd=kw.get("final_weight_decay"),
-                         start_lr=kw.get("start_lr"), ref_lr=kw.get("lr"), final_lr=kw.get("final_lr"),
-                         warmup=kw.get("warmup")) for kw in args_opt.get("multihead_kwargs")])
+    c = probe.read_config(args_eval, resume_preempt, num_heads=16)
+    args_data = args_eval.get("experiment").get("data")
+    c.update(num_workers=args_eval.get("num_workers", 0),
+             dataset_name=args_data.get("dataset_name"), num_classes=args_data.get("num_classes"),
+             root_path=args_data.get("root_path", None), image_folder=args_data.get("image_folder", None),
+             normalization=args_data.get("normalization", None),
+             num_samples=args_data.get("num_samples"), num_val_samples=args_data.get("num_val_samples"))
+    return c
 
 
 def output_paths(pretrain_folder, eval_tag, rank=0):
     """eval.py:121-127: (folder, log file, latest.pt)."""
-    folder = os.path.join(pretrain_folder, "image_classification_frozen/")
-    if eval_tag is not None:
-        folder = os.path.join(folder, eval_tag)
-    return folder, os.path.join(folder, f"log_r{rank}.csv"), os.path.join(folder, "latest.pt")
+    return probe.output_paths(pretrain_folder, "image_classification_frozen", eval_tag, rank)
 
 
 def main(args_eval, resume_preempt=False):
     """eval.py:49-260. Returns the best head's validation accuracy (%) of the last epoch run."""
-    world_size, rank = vcf._env_world_size(), 0
+    world_size, rank = env_world_size(), 0
     if world_size > 1:  # first: before the config is read, the checkpoint opened or a folder made
         raise NotImplementedError(f"image_classification_frozen on the HIP path runs on one GPU (world size "
                                   f"{world_size} requested): the multi-GPU run is not ported")
     c = read_config(args_eval, resume_preempt)
     val_only, batch_size, num_epochs, use_bfloat16 = c["val_only"], c["batch_size"], c["num_epochs"], c["use_bfloat16"]
-    if not torch.cuda.is_available():
-        raise RuntimeError("the frozen-encoder probe on the HIP path needs an MI355X (no CPU path)")
-    device = torch.device("cuda", 0)
-    torch.cuda.set_device(device)
-    np.random.seed(_GLOBAL_SEED)
-    torch.manual_seed(_GLOBAL_SEED)
-
+    device = init_device("the frozen-encoder probe")
     folder, log_file, latest_path = output_paths(c["pretrain_folder"], c["eval_tag"], rank)
     os.makedirs(folder, exist_ok=True)
     csv_logger = CSVLog(log_file)
@@ -227,10 +188,7 @@ def main(args_eval, resume_preempt=False):
 
     start_epoch = 0
     if c["resume_checkpoint"] and os.path.exists(latest_path):
-        *_, start_epoch = vcf.load_checkpoint(latest_path, classifiers, optimizer, scaler, val_only=val_only)
-        for _ in range(start_epoch * ipe):
-            [s.step() for s in scheduler]
-            [s.step() for s in wd_scheduler]
+        start_epoch = resume(latest_path, classifiers, optimizer, scaler, scheduler, wd_scheduler, ipe, val_only)
 
     val_acc = None
     for epoch in range(start_epoch, num_epochs):
@@ -242,6 +200,5 @@ def main(args_eval, resume_preempt=False):
         csv_logger.log(epoch + 1, train_acc, val_acc)
         if val_only:
             return val_acc
-        # through the module attribute, so that a caller who wraps the video eval's function sees this one too
-        vcf.save_checkpoint(latest_path, classifiers, optimizer, scaler, epoch + 1, batch_size, world_size)
+        save_checkpoint(latest_path, classifiers, optimizer, scaler, epoch + 1, batch_size, world_size)
     return val_acc
